@@ -3,18 +3,23 @@
 synthetic 64-agent / 1024-polyline / 128-light scene, W teacher-forced prime steps (untimed warm-up) + K closed-loop
 steps (timed), hipGraph replays).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes S] [--rollouts R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes S] [--rollouts R] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps once and prints the line (`value`, `ms_per_step` of that timed region). `--full` adds
+everything else this file measures: 3 repeats (median), the per-kernel roofline pass, the rule-check and new-scene figures, the appended
+WOSAC / submission / batched / bf16 / training measurements, the CPU baseline and the detail file. `--dump-outputs DIR` writes the
+rollout log of the last timed region (or the training step's metrics) as DIR/<name>.npy (tools/benchlib/outputs.py).
 
 One process per GPU; scenes / rollouts are independent, so ranks never communicate on the data path (weak scaling: every rank
 simulates its own scenes); the only collectives are the timing barrier and a MAX over ranks of the wall time (+ the gradient
 all-reduce of the training measurement). `python bench.py --gpus N` WITHOUT a launcher starts its N ranks itself, as fresh child
 processes, before anything touches the GPU (tools/benchlib/launch.py). Rank 0 prints ONE compact JSON line (< 8 KB, last line of
-stdout); per-kernel arrays, repeats and notes go to the detail file (gpurun_out/bench_detail.json) and a short table to stderr.
+stdout); with --full, per-kernel arrays, repeats and notes go to the detail file (report.write_detail) and a short table to stderr.
 
 The pieces live in tools/benchlib/: args (command line), launch (self-spawn), rollout (the timed region), training, events
-(per-kernel HIP-event passes -> `roofline`), cpu (`cpu_baseline`: the oracle on the host cores), report (the line).
-`value` / `ms_per_step` are the MEDIAN of `--repeats` timed regions on one engine, rewound in between. `roofline` describes the
+(per-kernel HIP-event passes -> `roofline`), cpu (`cpu_baseline`: the oracle on the host cores), report (the line), outputs (--dump-outputs).
+`value` / `ms_per_step` are the MEDIAN of `--repeats` timed regions on one engine, rewound in between. `roofline` (--full) describes the
 kernel class with the largest share of the timed schedule, measured live with HIP events around every launch of a few extra
 eager steps on the launch stream; `traffic` comes from the committed PMC passes (profiles/*pmc*.json, separate rocprofv3 --pmc
 runs of the same workload)."""
@@ -109,6 +114,15 @@ def dry_run(args, rank, world, report):
         dist.destroy_process_group()
 
 
+def dump_outputs(res, args, rank):
+    """--dump-outputs: rank 0 writes the headline measurement's outputs (popped from `res` either way: they are not part of the line)."""
+    arrays = res.pop("outputs", None)
+    if arrays is not None and rank == 0:
+        from tools.benchlib import outputs
+
+        outputs.write(arrays, args.dump_outputs)
+
+
 def main(argv=None):
     args = parse(argv)
     if launch.needs_spawn(args.gpus):
@@ -145,18 +159,21 @@ def main(argv=None):
     tb = load_package()
     hip = import_module("trafficbots_amd.hip")
     hip.load()  # raises if libtbx_hip.so is missing: there is no fallback path
+    detail_file = args.detail_file if (args.full or args.detail_file) else "-"
     if args.mode == "train":
-        full = training.train_main(args, tb, dev, rank, world, dist)
+        full = training.train_main(args, tb, dev, rank, world, dist, keep_outputs=bool(args.dump_outputs))
+        dump_outputs(full, args, rank)
         if rank == 0:
-            report.emit(full, args.detail_file)
+            report.emit(full, detail_file)
         if world > 1:
             dist.destroy_process_group()
         return
 
-    def measure(a):
-        return rollout.measure(a, tb, hip, dev, rank, world, dist)
+    def measure(a, keep_outputs=False):
+        return rollout.measure(a, tb, hip, dev, rank, world, dist, keep_outputs=keep_outputs)
 
-    res, wm, full_batch = measure(args)
+    res, wm, full_batch = measure(args, keep_outputs=bool(args.dump_outputs))
+    dump_outputs(res, args, rank)
     full = {"metric": "sim-agent-steps/sec (closed-loop rollout)", "value": res.pop("value"), "unit": "sim-agent-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res.pop("ms_per_step"),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -243,7 +260,7 @@ def main(argv=None):
         if not args.no_cpu_baseline and world == 1:
             full["cpu_baseline"] = cpu.cpu_baseline(tb, wm, full_batch, args)
             full["speedup_vs_cpu_baseline"] = full["value"] / full["cpu_baseline"]["value"]
-        report.emit(full, args.detail_file)
+        report.emit(full, detail_file)
     if world > 1:
         dist.destroy_process_group()
 

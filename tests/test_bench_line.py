@@ -249,3 +249,54 @@ def test_trace_average_comes_from_this_rounds_kernel_stats(tmp_path, monkeypatch
     e = events.kernel_entry(_args(), c)
     assert e["avg_launch_us_trace"] == 24.1 and e["trace_source"] == "r06_c2_kernel_stats.md"
     assert abs(e["frac_at_trace_avg"] - 7990400 / 24.1e-6 / 1e9 / 8000.0) < 1e-9 and e["frac_at_trace_avg"] > e["frac"]
+
+
+# ---- a plain run times the headline alone; --full keeps every other measurement; --dump-outputs writes what was timed
+def test_plain_run_measures_the_headline_only_and_full_keeps_the_rest():
+    from tools.benchlib.args import parse
+
+    a = parse([])
+    assert (a.steps, a.warmup, a.repeats, a.profile_steps, a.new_scenes) == (80, 10, 1, 0, 0)
+    assert a.no_cpu_baseline and not (a.wosac_shape or a.train_shape or a.bf16_shape or a.submission_shape or a.batched_shape or a.rule_checks)
+    a = parse(["--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.repeats) == (7, 3, 1) and a.dump_outputs is None
+    f = parse(["--full"])
+    assert (f.repeats, f.profile_steps, f.new_scenes) == (3, 3, 8) and not f.no_cpu_baseline
+    assert f.wosac_shape and f.train_shape and f.bf16_shape and f.submission_shape and f.batched_shape and f.rule_checks
+    f = parse(["--full", "--no-wosac-shape", "--no-cpu-baseline", "--profile-steps", "0"])
+    assert f.no_cpu_baseline and not f.wosac_shape and not f.rule_checks and f.repeats == 3
+    t = parse(["--mode", "train"])
+    assert (t.steps, t.warmup, t.profile_steps) == (10, 3, 0) and parse(["--mode", "train", "--full"]).profile_steps == 3
+
+
+def test_dump_outputs_are_float_arrays_sampled_the_same_way_every_time(tmp_path):
+    import numpy as np
+    import torch
+
+    from tools.benchlib import outputs
+
+    g = torch.Generator().manual_seed(5)
+    small = {"out_pose": torch.randn(2, 8, 10, 3, generator=g), "out_valid": torch.randint(0, 2, (2, 8, 10), dtype=torch.uint8, generator=g),
+             "loss": torch.tensor(1.25, dtype=torch.float64)}
+    a = outputs.collect(small)
+    assert sorted(a) == ["loss", "out_pose", "out_valid"]
+    assert a["out_pose"].dtype == np.float32 and a["out_valid"].dtype == np.float32 and a["loss"].dtype == np.float64
+    assert np.array_equal(a["out_pose"], small["out_pose"].numpy()) and np.array_equal(a["out_valid"], small["out_valid"].float().numpy())
+    # above the budget: a fixed, seeded sample of every array, its flat indices beside it
+    big = {"out_pose": torch.arange(300_000, dtype=torch.float32).reshape(100, 1000, 3), "out_tf": torch.ones(50_000, dtype=torch.uint8)}
+    b1, b2 = outputs.collect(big, max_bytes=400_000), outputs.collect(big, max_bytes=400_000)
+    assert sorted(b1) == ["out_pose", "out_pose.sample_index", "out_tf", "out_tf.sample_index"]
+    outputs.write(b1, tmp_path / "b")
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 400_000  # every file written: values, indices, headers
+    assert b1["out_pose"].size > 20_000  # (and the sample uses that budget: 400 kB / 12 B per element, over 350,000 elements)
+    for k in b1:
+        assert np.array_equal(b1[k], b2[k]), k
+    idx = b1["out_pose.sample_index"]
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and np.array_equal(b1["out_pose"], idx.astype(np.float32))
+    # the default budget against a log larger than it (200 MB of float32 values): what lands on disk stays within 60 MB
+    huge = {"a": torch.zeros(40_000_000), "b": torch.zeros(10_000_000, dtype=torch.uint8)}
+    outputs.write(outputs.collect(huge), tmp_path / "h")
+    assert sum(f.stat().st_size for f in (tmp_path / "h").iterdir()) <= outputs.MAX_BYTES <= 64_000_000
+    names = outputs.write(a, tmp_path / "d")
+    assert names == ["loss", "out_pose", "out_valid"]
+    assert np.array_equal(np.load(tmp_path / "d" / "out_pose.npy"), a["out_pose"])

@@ -1,7 +1,7 @@
 """Multi-GPU readiness on ONE GPU (no 8-GPU node exists for the builder): the data-parallel training step
 through the real exchange path - a one-rank RCCL process group on the device (torch.distributed backend "nccl" IS RCCL on ROCm):
 `broadcast_parameters`, the flat gradient all-reduce of `allreduce_gradients` inside `train_step` and after `GraphedTrainStep`'s
-graph replay, per-rank seed separation, and that `bench.py --mode train --gpus 1` reports what the default line's `training`
+graph replay, per-rank seed separation, and that `bench.py --mode train --gpus 1` reports what the --full line's `training`
 entry reports. No scaling curve is measured here (DESIGN.md 7 says so)."""
 import json
 import os
@@ -104,7 +104,7 @@ def test_one_rank_rccl_training_step_takes_the_real_exchange_path(tmp_path):
 
 
 def test_bench_train_mode_agrees_with_the_default_lines_training_entry():
-    """`bench.py --mode train --gpus 1` and the `training` entry the default line appends run the same step: same metric, config
+    """`bench.py --mode train --gpus 1` and the `training` entry a --full line appends run the same step: same metric, config
     and all-reduce size; throughput within the run-to-run spread of a 2-step measurement."""
     a = json.loads(_run([sys.executable, "bench.py", "--mode", "train", "--gpus", "1", "--scenes", "2", "--steps", "2", "--warmup", "1",
                          "--agents", "32", "--polylines", "128", "--lights", "32"]).strip().splitlines()[-1])

@@ -6,7 +6,7 @@ out=gpurun_out/${tag}_attn_ab.txt
 : > $out
 for kv in "" "--kv-bf16"; do
   for p in 0 1; do
-    python3 bench.py --agents 128 --rollouts 32 --scenes 1 --steps 40 --no-cpu-baseline --new-scenes 0 $kv --attn-mfma $p --detail-file - 2>/dev/null | tail -1 |
+    python3 bench.py --full --agents 128 --rollouts 32 --scenes 1 --steps 40 --no-cpu-baseline --new-scenes 0 $kv --attn-mfma $p --detail-file - 2>/dev/null | tail -1 |
       python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())

@@ -8,7 +8,7 @@ C=trafficbotsv1.5_amd/csrc
 timeout 900 python -m pytest tests/test_hip_parity.py tests/test_hip_bf16.py -m gpu -q -x 2>&1 | tail -4 > $out/ab_tile_tests.log
 run() {  # name, lib, args...
   local name=$1 lib=$2; shift 2
-  TBX_HIP_LIB=$lib timeout 600 python bench.py --no-cpu-baseline --no-wosac-shape --no-train-shape --no-bf16-shape --no-rule-checks --no-submission-shape --no-batched-shape --profile-steps 0 --new-scenes 0 "$@" 2>/dev/null | tail -1 | python -c "
+  TBX_HIP_LIB=$lib timeout 600 python bench.py --full --no-cpu-baseline --no-wosac-shape --no-train-shape --no-bf16-shape --no-rule-checks --no-submission-shape --no-batched-shape --profile-steps 0 --new-scenes 0 "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$name', d['value'], d['ms_per_step'])"
 }

@@ -6,4 +6,5 @@
   events.py    per-kernel-class HIP-event passes (the `roofline` objects) + the committed PMC passes' traffic
   cpu.py       the oracle on the host cores (`cpu_baseline`)
   report.py    the ONE judged JSON line (compact, < 8 KB) and the detail side file
+  outputs.py   --dump-outputs: what the timed path computed, as .npy files
 """

@@ -7,8 +7,10 @@ from importlib import import_module
 
 import torch
 
-from . import events
+from . import events, outputs
 from .args import shard_scenes
+
+PRE_ROLL_MAX_STEPS = 400  # a pre-roll replay is at most this many steps: the warm-up stays ~pre_roll_ms however long the timed region
 
 
 def build(tb, args, dev, rank):
@@ -122,9 +124,10 @@ def rule_check_leg(a, wm, eng, use_graph, barrier, reduce_max):
                     "tbx_rule_accumulate (+ tbx_filter_futures for > 32 futures), timed together; rule_checks_ms = device time of that tail"}
 
 
-def measure(a, tb, hip, dev, rank, world, dist):
+def measure(a, tb, hip, dev, rank, world, dist, keep_outputs=False):
     """-> (result dict, wm, full). The result holds `value`, `ms_per_step`, the repeats, `config`, `roofline`, `kernels`, the
-    end-to-end figures; report.py decides what of it goes on the judged line."""
+    end-to-end figures; report.py decides what of it goes on the judged line. keep_outputs: also `outputs`, the rollout log of the
+    last timed region as host arrays (outputs.py)."""
     E = import_module("trafficbots_amd.engine")
 
     def barrier():
@@ -153,10 +156,10 @@ def measure(a, tb, hip, dev, rank, world, dist):
     # device pre-roll (untimed, not part of W): the timed region is ~25 ms of a chain of 20-40 us launches, and a device that
     # was idle a moment ago runs its first hundreds of milliseconds below its steady clocks (the same binary measured 193 k,
     # 195 k, 200 k agent-steps/s in three consecutive processes). Whole rollouts are replayed and rewound until
-    # --pre-roll-ms of wall time have passed.
+    # --pre-roll-ms of wall time have passed (a rollout longer than PRE_ROLL_MAX_STEPS is replayed in part).
     t_pre, n_pre = time.perf_counter(), 0
     while use_graph and (time.perf_counter() - t_pre) * 1e3 < a.pre_roll_ms:
-        eng.run(a.warmup + a.steps, use_graph=True)
+        eng.run(min(a.warmup + a.steps, PRE_ROLL_MAX_STEPS), use_graph=True)
         torch.cuda.synchronize()
         eng.restore()
         n_pre += 1
@@ -179,6 +182,8 @@ def measure(a, tb, hip, dev, rank, world, dist):
     units = world * a.scenes * a.rollouts * a.agents * a.steps
     timing = {"value": units / dt, "ms_per_step": dt / a.steps * 1e3, "repeats": len(dts), "ms_per_step_min": min(dts) / a.steps * 1e3,
               "ms_per_step_all": [d / a.steps * 1e3 for d in dts], "value_best": units / min(dts)}
+    if keep_outputs:  # (before anything below rewinds the engine)
+        timing["outputs"] = outputs.collect(outputs.rollout_outputs(eng, a.warmup + a.steps))
     if getattr(a, "rule_checks", False):
         def reduce_max(x):
             if world > 1:
@@ -272,9 +277,9 @@ def measure(a, tb, hip, dev, rank, world, dist):
                 "one_queue_paired_launches": bool(eng.one_queue),  # Schedule.one_queue: 5 paired launches per step, the lights one step ahead in the same grids
                 "attn_mfma": wm.schedule.attn_mfma,
                 "weights": "random init of the 10,657,094-parameter default architecture"}
-    if a.profile_steps <= 0:  # tooling only (timeline traces, A/B runs, the scenes-per-GPU curve): no per-kernel timing pass
+    if a.profile_steps <= 0:  # a plain run, and tooling (timeline traces, A/B runs, the scenes-per-GPU curve): no per-kernel timing pass
         return {**timing, "config": workload, "roofline": None, "kernels": None,
-                "note": "--profile-steps 0: no per-kernel timing pass, not a judged line",
+                "note": "--profile-steps 0: no per-kernel timing pass (a plain run's default; --full adds it)",
                 "scene_encode_ms": t_scene * 1e3, "graph_capture_ms": t_cap * 1e3,
                 "finite": bool(torch.isfinite(eng.S["out_pose"]).all())}, wm, full
     # ---- live per-kernel timing: eager steps right after the timed region, same state and the SAME launches as the timed

@@ -6,11 +6,12 @@ from importlib import import_module
 
 import torch
 
-from . import events
+from . import events, outputs
 from .args import shard_scenes
 
 
-def train_main(args, tb, dev, rank, world, dist):
+def train_main(args, tb, dev, rank, world, dist, keep_outputs=False):
+    """keep_outputs: the result also holds `outputs`, the metrics of the last timed step as host arrays (outputs.py)."""
     W = import_module("trafficbots_amd.pl_modules.waymo_motion")
     DP = import_module("trafficbots_amd.pl_modules.data_parallel")
     # library GEMMs of the training step through rocBLAS: hipBLASLt's pick for the [n*A*W, 64] x [64, 128] input-gradient GEMMs
@@ -58,6 +59,7 @@ def train_main(args, tb, dev, rank, world, dist):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    kept = outputs.collect(outputs.train_outputs(m)) if keep_outputs else None
     n_live = sum(p.numel() for p in (live or []))
     # ---- per-kernel pass (untimed): ONE eager step with HIP events around this repo's kernels; what is not wrapped (library
     # GEMMs, aten elementwise) is the remainder of the step's GPU time, measured by an event pair around the whole step
@@ -82,4 +84,4 @@ def train_main(args, tb, dev, rank, world, dist):
                        "allreduce_bytes": n_live * 4, "note": "time-batched rollout (stepping pass + one differentiated policy batch over the 90 steps); dropout as configured (p=0.1) with keyed masks: residual / FFN / MLP through tbx_keyed_dropout, "
                                                              "attention probabilities inside the HIP attention kernels"},
             "roofline": roof, "kernels": kernels,
-            "loss": float(m["loss"]), "finite": bool(torch.isfinite(m["loss"]))}
+            "loss": float(m["loss"]), "finite": bool(torch.isfinite(m["loss"])), **({"outputs": kept} if keep_outputs else {})}

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 tag=${TAG:-r04}
 out=gpurun_out/pmc_busy; mkdir -p $out
-common="--no-cpu-baseline --no-wosac-shape --no-lights-ahead --no-graph --profile-steps 0 --steps 6 --warmup 2 --new-scenes 0 --detail-file -"
+common="--full --no-cpu-baseline --no-wosac-shape --no-lights-ahead --no-graph --profile-steps 0 --steps 6 --warmup 2 --new-scenes 0 --detail-file -"
 declare -A W
 W[c2]="bench.py $common"
 W[c5]="bench.py $common --agents 128 --rollouts 32 --scenes 1"

@@ -21,10 +21,10 @@ rm -rf /tmp/tl_final
 ( cd /tmp && export TMPDIR=/tmp && TBX_ONE_QUEUE=0 rocprofv3 --kernel-trace -d /tmp/tl_final -o tl -- python3 $root/bench.py --no-cpu-baseline --no-wosac-shape --no-train-shape --no-bf16-shape --profile-steps 0 --new-scenes 0 > /dev/null 2>&1 )
 python3 tools/step_timeline2.py $(ls /tmp/tl_final/*.db | head -1) > gpurun_out/${tag}_c2_two_stream_timeline.txt 2>&1
 rm -rf /tmp/tl_final
-{ F="--no-cpu-baseline --no-wosac-shape --no-train-shape --no-bf16-shape --no-rule-checks --no-submission-shape --no-batched-shape --profile-steps 0 --new-scenes 0"; for v in 1 0 1 0; do echo "TBX_ONE_QUEUE=$v $(TBX_ONE_QUEUE=$v python bench.py $F 2>/dev/null | tail -1 | cut -c1-200)"; done; } > gpurun_out/${tag}_c2_one_queue_ab.txt
 out=$root/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 cd $root
+{ F="--full --no-cpu-baseline --no-wosac-shape --no-train-shape --no-bf16-shape --no-rule-checks --no-submission-shape --no-batched-shape --profile-steps 0 --new-scenes 0"; for v in 1 0 1 0; do echo "TBX_ONE_QUEUE=$v $(TBX_ONE_QUEUE=$v python bench.py $F 2>/dev/null | tail -1 | cut -c1-200)"; done; } > $out/${tag}_c2_one_queue_ab.txt
 rocprofv3 --kernel-trace --stats -d $out/kt_train -o kt -- python3 bench.py --mode train --no-cpu-baseline --no-train-graph --steps 1 --warmup 1 --profile-steps 0 > $out/${tag}_train_eager.log 2>&1
 db=$(find $out/kt_train -name '*.db' | head -1)
 { echo "rocprofv3 --kernel-trace --stats -- python3 bench.py --mode train --no-cpu-baseline --no-train-graph --steps 1 --warmup 1 --profile-steps 0  (2 eager training steps of 16 scenes; a graph replay takes the GPU-busy time of one)"; echo; tail -1 $out/${tag}_train_eager.log | cut -c1-300; echo; python3 tools/rocpd_stats.py $db 2>/dev/null | head -42; } > $out/${tag}_train_kernel_stats.md
@@ -60,7 +60,7 @@ python3 tools/step_timeline2.py $(ls /tmp/tl_s64/*.db | head -1) > $out/${tag}_s
 rm -rf /tmp/tl_s64
 timeout 300 python3 tools/scene_loop_profile.py 2>&1 | grep -v amdgpu.ids > $out/${tag}_scene_loop_profile.txt
 # the judged command, last: its line and its detail file
-timeout 900 python bench.py > $out/${tag}_bench_default.log 2>&1
+timeout 900 python bench.py --full > $out/${tag}_bench_default.log 2>&1
 grep -a '"metric"' $out/${tag}_bench_default.log | tail -1 > $out/${tag}_bench_line.json
 cp $out/bench_detail.json $out/${tag}_bench_detail.json
 tail -1 $out/${tag}_bench_default.log | cut -c1-200
