@@ -439,3 +439,72 @@ def test_clip_on_the_flat_gradient_buffer_equals_clip_grad_norm(tb):
             assert p.grad.data_ptr() == flat.views[i].data_ptr()  # still the flat buffer's slice
             torch.testing.assert_close(p.grad, q.grad, rtol=2e-6, atol=0)
         assert DP.clip_gradients(flat, 0) is None
+
+
+def test_derived_weight_images_follow_the_weights_stamp_and_the_scope(tb):
+    """hip_base._derived, the one cache of images derived from weights: a hit on repeat; a miss after an in-place op, after
+    increment_version (what FlatAdamW.step does after updating through its flat buffer) and after `q.data = other`; images made inside a
+    PackScope live in the scope, not on the Parameter, and die with it. packed_weight's requests recorded in a scope (a view, a whole
+    Parameter), rebuilt (_at) after the Parameters' `.data` was re-pointed, alias the new storage and keep their cache keys."""
+    import gc
+    import weakref
+
+    HB = import_module("trafficbots_amd.hip_base")
+    q = torch.nn.Parameter(torch.arange(6.0))
+    made = []
+
+    def get():
+        return HB._derived(("test", HB._name(q)), (q,), lambda: made.append(1) or q.detach() * 2)
+
+    a = get()
+    assert get() is a and len(made) == 1
+    with torch.no_grad():
+        q.add_(1.0)
+    assert torch.equal(get(), q.detach() * 2) and len(made) == 2
+    torch.autograd.graph.increment_version([q])
+    get()
+    assert len(made) == 3
+    flat = torch.zeros(10)
+    q.data = flat[2:8]
+    get()
+    assert len(made) == 4 and get() is not None and len(made) == 4
+    with torch.no_grad():
+        flat.add_(1.0)  # through the flat buffer: q's version counter does not see it ...
+    assert len(made) == 4 and get() is not None and len(made) == 4
+    torch.autograd.graph.increment_version([q])  # ... until it is bumped
+    assert torch.equal(get(), q.detach() * 2) and len(made) == 5
+    on_q = dict(q._tbx_derived)
+    scope = HB.open_pack_scope()
+    try:
+        b = get()
+        assert len(made) == 6 and get() is b and len(made) == 6
+        assert q._tbx_derived == on_q and id(q) in scope.pinned
+    finally:
+        HB.close_pack_scope(scope)
+    gone = weakref.ref(b)
+    del b, scope
+    gc.collect()
+    assert gone() is None
+    get()
+    assert len(made) == 6  # the Parameter's own image is still current
+    # packed_weight's requests, recorded in a scope of an owner (the images are seeded: packing needs the GPU), become the owner's plan;
+    # rebuilt on the Parameters' new storage, as open_pack_scope does, they alias it and keep the keys they were recorded under
+    owner, w2 = torch.nn.Module(), torch.nn.Parameter(torch.arange(12.0).view(3, 4))
+    reqs = [(w2[1:], q[2:5]), (w2, q[:3])]  # a view of each Parameter, and a whole Parameter with a view
+    scope = HB.open_pack_scope(owner, "k")
+    for w, bias in reqs:
+        key = HB._pack_key(w, bias, False, 1, False, False, True)
+        scope.images[key] = (HB.weights_stamp((w, bias)), "image")
+        assert HB.packed_weight(w, bias, mfma32=True) == "image"
+    HB.close_pack_scope(scope)
+    keys = list(scope.record)
+    assert len(keys) == 2 and [e[:2] for e in owner._tbx_pack_plans["k"]] == [scope.record[k][:2] for k in keys]
+    other, flat = torch.arange(20.0), torch.arange(30.0)
+    q.data, w2.data = other[7:13], flat[5:17].view(3, 4)
+    now = [(w2[1:], q[2:5]), (w2, q[:3])]  # the same requests on the new storage
+    for k, (wp, bp, wt, groups), (w, bias) in zip(keys, owner._tbx_pack_plans["k"], now):
+        v, vb = HB._at(wp), HB._at(bp)
+        assert HB._pack_key(v, vb, wt, groups, False, False, True) == k
+        assert v.data_ptr() == w.data_ptr() and torch.equal(v, w) and vb.data_ptr() == bias.data_ptr() and torch.equal(vb, bias)
+        assert v.data_ptr() >= flat.data_ptr() and vb.data_ptr() >= other.data_ptr()  # (the new storage)
+    assert HB._at(owner._tbx_pack_plans["k"][1][0]) is w2  # a whole Parameter is rebuilt as itself

@@ -263,6 +263,57 @@ def test_graphed_train_step_equals_eager_across_optimizer_steps(tb, monkeypatch,
         assert close(a, p.grad, 1e-3), names[id(p)]
 
 
+def test_rollout_after_flat_adamw_steps_runs_on_the_trained_weights(tb):
+    """Validation between training steps of GraphedTrainStep (FlatAdamW: the update goes through ONE flat buffer, not through the
+    parameters' own version counters): the rollout after two more steps must run on the trained weights - a new engine, bit for bit
+    the rollout of a fresh module loaded with the same state dict (no caches). Every derived weight image and engine is stamped with
+    the parameters' versions (hip_base.weights_stamp); without FlatAdamW.step bumping them the second validation reused the first one's
+    engine and images: stale weights, no error."""
+    dev = torch.device("cuda:0")
+    DP = import_module("trafficbots_amd.pl_modules.data_parallel")
+    W = import_module("trafficbots_amd.pl_modules.waymo_motion")
+    cfg = tb.config.default_model_cfg(n_tgt_knn=4)
+    cfg["tf_cfg"]["dropout_p"] = 0.0
+    cfg["mp_encoder"]["pl_encoder"]["mlp_dropout_p"] = 0.0
+    cfg["add_navi_latent"]["mlp_dropout_p"] = 0.0
+    scfg = tb.config.default_sim_cfg()
+    scfg["teacher_forcing_training"]["prob_forcing_agent"] = 0.0
+    scfg["pre_processing"]["scene_centric"]["dropout_p_history"] = -1.0
+    scfg["time_step_end"] = 30
+    torch.manual_seed(0)
+    wm = W.WaymoMotion(model=cfg, data_size=tb.synthetic.DATA_SIZE, **scfg).to(dev).train()
+    (opt,), _ = wm.configure_optimizers()
+    batch = {k: v.to(dev) for k, v in tb.synthetic.make_scene(2, 8, 64, 8, seed=0).items()}
+    gs = DP.GraphedTrainStep(wm, opt, batch)
+    assert gs.flat_opt is not None  # (the default: FlatAdamW)
+    scene = tb.synthetic.make_scene(1, 8, 64, 8, seed=11)
+    full = {k: v.to(dev) for k, v in {**scene, **tb.synthetic.to_history_batch(scene)}.items()}
+
+    def roll(m):
+        m.eval()
+        bd = m.pre_processing({k: v.clone() for k, v in full.items()})
+        mp, tl = m.encode_scene(bd, tl_valid_key="gt/tl_valid")
+        valid = bd["gt/ag_valid"].any(-1)
+        z = torch.randn(1, valid.shape[1], 16, generator=torch.Generator().manual_seed(1)).to(dev)
+        buf = m.reactive_replay(bd, mp, tl, z, valid, bd["gt/ag_navi"], valid, m.teacher_forcing_joint_future_pred, True, step_end=24)
+        return buf, m._engine
+
+    for _ in range(2):
+        gs(batch)
+    first, eng0 = roll(wm)
+    wm.train()
+    for _ in range(2):
+        gs(batch)
+    got, eng1 = roll(wm)
+    fresh = W.WaymoMotion(model=cfg, data_size=tb.synthetic.DATA_SIZE, **scfg).to(dev)
+    fresh.load_state_dict(wm.state_dict())
+    ref, _ = roll(fresh)
+    assert not torch.equal(first.pred_pose, ref.pred_pose)  # the training steps did move the rollout
+    assert torch.equal(got.pred_pose, ref.pred_pose) and torch.equal(got.vis_dict["action"], ref.vis_dict["action"])
+    assert torch.equal(got.vis_dict["tl_state"], ref.vis_dict["tl_state"]) and torch.equal(got.tl_state_nll, ref.tl_state_nll)
+    assert eng1 is not eng0
+
+
 def test_attention_probability_dropout_vs_explicit_mask(tb):
     """tbx_knarpe_attn_fwd_dropout / _bwd_dropout (attention_rpe.py:171-172 inside the kernels) against explicit torch math with
     the mask the (seed, call) pair produces (hip.dropout_keep_mask restates the kernels' counter hash): forward outputs and

@@ -1,5 +1,6 @@
 """ctypes glue shared by the hip_* wrapper modules: return-code check, device-pointer helpers, the current stream, the attention
-segment descriptor and the weight-image caches (tbx_pack_weight* images per parameter version, or per training step inside PACK_SCOPE).
+segment descriptor and the cache of images derived from weights (tbx_pack_weight* images, padded and stacked copies: per weights
+version, or per training step inside a PackScope).
 There is no CPU path: every helper raises on tensors that are not on a HIP device."""
 import ctypes as C
 import os
@@ -66,57 +67,112 @@ def _drop_args(drop):
     return p, seed, call, int(tb), int(t0)
 
 
-def padded_weight(w: torch.Tensor, k_pad: int) -> torch.Tensor:
-    """w [n, k] zero-padded to k_pad columns; cached like packed_weight (per parameter version, or per training step in PACK_SCOPE)."""
-    if w.shape[1] == k_pad:
-        return w
-    key = ("padded", id(w), k_pad)
-    stamp = (w._version, w.data_ptr())
-    cache = PACK_SCOPE if PACK_SCOPE is not None else w.__dict__.setdefault("_tbx_padded", {})
+def weights_stamp(tensors) -> tuple:
+    """(version, data_ptr) of each tensor that is not None: THE freshness rule of images derived from weights (_derived, WaymoMotion's
+    rollout engines). An in-place update (optimizer step, load_state_dict) bumps the version; `p.data = ` or `.to()` moves the storage."""
+    return tuple([(t._version, t.data_ptr()) for t in tensors if t is not None])
+
+
+class PackScope:
+    """The derived weight images of one training step (open_pack_scope .. close_pack_scope; reopen_pack_scope for its backward): each weight
+    is packed ONCE PER STEP into the scope, not into the per-Parameter cache. A captured step (GraphedTrainStep) replays after the optimizer
+    has moved the weights: an image cached before the capture would never be re-packed (its launch is not in the graph)."""
+
+    def __init__(self, plans: Optional[dict] = None, plan_key=None):
+        self.images = {}  # _derived's entries: key -> (stamp, image)
+        self.pinned = {}  # id -> tensor: the sources of images and groups, alive while the scope is (the ids in keys stay unique)
+        self.groups = {}  # id(tensor) -> pack_group's requests
+        self.plans, self.plan_key = plans, plan_key  # the owner's recorded lists (None: no owner) and this scope's key in them
+        self.record = {}  # pack key -> (_place(weight), _place(bias), wt, groups) of this scope's Parameter-sourced mfma32 requests
+
+
+_PACK_SCOPE: Optional[PackScope] = None  # the open scope: written by open_ / reopen_ / close_pack_scope only
+
+
+def _place(t: Optional[torch.Tensor]):
+    """(base tensor, offset relative to the base's, shape, stride) of a view; (t,) of a tensor that is no view; None for None. A view of
+    an nn.Parameter is described by the Parameter, not by its storage: the description survives `p.data = ...` (FlatAdamW re-points the
+    weights into one buffer)."""
+    if t is None:
+        return None
+    base = t._base
+    if base is None:
+        return (t,)
+    return base, t.storage_offset() - base.storage_offset(), t.shape, t.stride()
+
+
+def _at(place):
+    """The tensor a _place describes, on its base tensor's CURRENT storage (None for None)."""
+    if place is None or len(place) == 1:
+        return place if place is None else place[0]
+    base, off, shape, stride = place
+    with torch.no_grad():
+        return base.as_strided(shape, stride, base.storage_offset() + off)
+
+
+def _name(t: Optional[torch.Tensor]):
+    """t's part of a cache key: its _place with the base tensor's id (restated: this runs on every cache hit)."""
+    if t is None:
+        return None
+    base = t._base
+    if base is None:
+        return id(t)
+    return id(base), t.storage_offset() - base.storage_offset(), t.shape, t.stride()
+
+
+def _derived(key: tuple, sources, make=None, *args):
+    """The image `key` (which names `sources`: tensors or None) while weights_stamp(sources) holds, else make(*args)'s, stored - in the
+    open scope (the sources pinned) or on the first source's base tensor (dropped with the Parameter). make=None: look up only (None on a
+    miss). A hit builds nothing: `make` is a module-level function, not a closure."""
+    stamp, scope = weights_stamp(sources), _PACK_SCOPE
+    if scope is not None:
+        cache = scope.images
+    else:
+        owner = sources[0]._base
+        owner = sources[0] if owner is None else owner
+        cache = getattr(owner, "_tbx_derived", None)
+        if cache is None:
+            cache = owner._tbx_derived = {}
     hit = cache.get(key)
     if hit is not None and hit[0] == stamp:
         return hit[1]
-    with torch.no_grad():
-        out = torch.zeros(w.shape[0], k_pad, dtype=torch.float32, device=w.device)
-        out[:, :w.shape[1]].copy_(w)
+    if make is None:
+        return None
+    out = make(*args)
     cache[key] = (stamp, out)
-    if PACK_SCOPE is not None:
-        PACK_SCOPE.setdefault("_keep", {})[id(w)] = w
+    if scope is not None:
+        scope.pinned.update((id(t), t) for t in sources if t is not None)
     return out
 
 
-# Set to a dict for the duration of a training step (train_graph.training_step): chain kernels of the step's no-grad stepping
-# pass then pack each weight ONCE PER STEP into this scope instead of the per-parameter cache. A captured training step
-# (GraphedTrainStep) replays after the optimizer has moved the weights: a cached image from before the capture would be read by
-# the replay without ever being re-packed (its tbx_pack_weight launch is not in the graph) - with the scope the packing is.
-PACK_SCOPE: Optional[dict] = None
+def padded_weight(w: torch.Tensor, k_pad: int) -> torch.Tensor:
+    """w [n, k] zero-padded to k_pad columns; a derived image (_derived: per weights version, or per training step in a PackScope)."""
+    if w.shape[1] == k_pad:
+        return w
+    return _derived(("padded", _name(w), k_pad), (w,), _make_padded, w, k_pad)
 
 
-def _pack_key(w, bias, wt, groups, split, gemv, mfma32):
-    """-> (cache dict, key, stamp) of a packed_weight request (see there)."""
-    base = w._base if w._base is not None else w
-    bkey = None if bias is None else (bias.data_ptr(), bias.shape[0])
-    key = (w.storage_offset(), tuple(w.shape), w.stride(0), wt, groups, bkey, split, gemv, mfma32)
-    if PACK_SCOPE is not None:  # a training step: images live (and are re-packed) per step, see PACK_SCOPE
-        cache, key = PACK_SCOPE, (id(base),) + key
-        PACK_SCOPE.setdefault("_keep", {})[id(base)] = base  # ids stay unique while the scope lives
-    else:
-        cache = base.__dict__.setdefault("_tbx_packed", {})
-    return cache, key, (w._version, w.data_ptr(), None if bias is None else bias._version)
+@torch.no_grad()
+def _make_padded(w, k_pad):
+    out = torch.zeros(w.shape[0], k_pad, dtype=torch.float32, device=w.device)
+    out[:, :w.shape[1]].copy_(w)
+    return out
+
+
+def _pack_key(w, bias, wt, groups, split, gemv, mfma32) -> tuple:
+    return ("pack", _name(w), _name(bias), wt, groups, split, gemv, mfma32)
 
 
 def packed_weights_mfma32_multi(reqs) -> None:
     """reqs = [(w, bias | None, wt, groups)]: the tbx_pack_weight_mfma32 images of all of them in ONE launch
-    (tbx_pack_weight_mfma32_multi), left in the cache packed_weight(.., mfma32=True) looks them up in. Requests whose image is current
-    are skipped."""
+    (tbx_pack_weight_mfma32_multi), left where packed_weight(.., mfma32=True) looks them up. Requests whose image is current are skipped."""
     from .abi import PackJob
 
-    lib, jobs, keep = load(), [], []
+    lib, jobs, made = load(), [], []
     for w, bias, wt, groups in reqs:
         assert w.is_cuda and w.dim() == 2 and w.stride(1) == 1 and w.dtype == torch.float32
-        cache, key, stamp = _pack_key(w, bias, wt, groups, False, False, True)
-        hit = cache.get(key)
-        if hit is not None and hit[0] == stamp:
+        key = _pack_key(w, bias, wt, groups, False, False, True)
+        if _derived(key, (w, bias)) is not None:
             continue
         n, k = (w.shape[1], w.shape[0] // groups) if wt else (w.shape[0] // groups, w.shape[1])
         size = lib.tbx_pack_weight_mfma32_size(n, k, groups)
@@ -128,76 +184,86 @@ def packed_weights_mfma32_multi(reqs) -> None:
         j = PackJob()
         j.w, j.bias, j.out, j.n, j.k, j.ld, j.groups, j.wt = _ptr(w), _ptr(bias), _ptr(out), n, k, w.stride(0), groups, int(wt)
         jobs.append(j)
-        keep.append((cache, key, stamp, out))
+        made.append((key, (w, bias), out))
     if not jobs:
         return
     arr = (PackJob * len(jobs))(*jobs)
     _check(lib.tbx_pack_weight_mfma32_multi(arr, len(jobs), stream_ptr()), "tbx_pack_weight_mfma32_multi")
-    for cache, key, stamp, out in keep:
-        cache[key] = (stamp, out)
+    for key, sources, out in made:
+        _derived(key, sources, lambda: out)  # (a miss: this closure is not on the hit path)
 
 
 def pack_group(tensors, reqs) -> None:
-    """Inside a PACK_SCOPE: the first packed_weight(.., mfma32=True) request for any of `tensors` packs ALL of `reqs` in one launch (the
+    """Inside a PackScope: the first packed_weight(.., mfma32=True) request for any of `tensors` packs ALL of `reqs` in one launch (the
     folded weights of an attention module: its three LINEARs' images and the W^T images of their input gradients)."""
-    if PACK_SCOPE is None:
+    if _PACK_SCOPE is None:
         return
-    g = PACK_SCOPE.setdefault("_groups", {})
-    keep = PACK_SCOPE.setdefault("_keep", {})
     reqs = list(reqs)
     for t in tensors:
-        g[id(t)] = reqs
-        keep[("group", id(t))] = t
+        _PACK_SCOPE.groups[id(t)] = reqs
+        _PACK_SCOPE.pinned[id(t)] = t
 
 
 # The image requests of a training step whose sources are nn.Parameters (ready when the step starts) are kept, per owner (the model:
 # the list dies with it) and key, as recorded during the previous step: open_pack_scope packs all of them in ONE launch (a 16-scene step
-# asked for ~80 of them one by one, forward and backward).
-def open_pack_scope(owner=None, plan_key=None) -> dict:
-    """PACK_SCOPE = a new scope; with a list recorded for (owner, plan_key), its images first (one launch). -> the scope."""
-    global PACK_SCOPE
-    plans = None if owner is None else owner.__dict__.setdefault("_tbx_pack_plans", {})
-    PACK_SCOPE = {"_plans": plans, "_plan_key": plan_key, "_record": {}}
+# asked for ~80 of them one by one, forward and backward). An entry names its Parameters and the views' places in them (_place), so
+# the views are rebuilt on the Parameters' current storage.
+def open_pack_scope(owner=None, plan_key=None) -> PackScope:
+    """Open a new PackScope; with a list recorded for (owner, plan_key), its images first (one launch). -> the scope."""
+    global _PACK_SCOPE
+    plans = None if owner is None else getattr(owner, "_tbx_pack_plans", None)
+    if owner is not None and plans is None:
+        plans = owner._tbx_pack_plans = {}
+    _PACK_SCOPE = scope = PackScope(plans, plan_key)
     plan = plans.get(plan_key) if plans is not None else None
     if plan:
-        plan = [r for r in plan if r[0].is_cuda and (r[1] is None or r[1].is_cuda)]  # (a model moved off the device since: nothing to pre-pack)
-        packed_weights_mfma32_multi(plan)
-        for r in plan:
-            PACK_SCOPE["_record"][_pack_key(r[0], r[1], r[2], r[3], False, False, True)[1]] = r
-    return PACK_SCOPE
+        plan = [e for e in plan if e[0][0].is_cuda and (e[1] is None or e[1][0].is_cuda)]  # (a model moved off the device: not packed)
+        reqs = [(_at(w), _at(b), wt, groups) for w, b, wt, groups in plan]
+        packed_weights_mfma32_multi(reqs)
+        for e, r in zip(plan, reqs):
+            scope.record[_pack_key(r[0], r[1], r[2], r[3], False, False, True)] = e
+    return scope
 
 
-def close_pack_scope(scope: Optional[dict] = None) -> None:
-    """PACK_SCOPE = None; the scope's Parameter-sourced requests become the list the next scope of its owner and key starts from."""
-    global PACK_SCOPE
-    scope = PACK_SCOPE if scope is None else scope
-    if scope is not None and scope.get("_plans") is not None:
-        scope["_plans"][scope["_plan_key"]] = list(scope["_record"].values())
-    PACK_SCOPE = None
+def reopen_pack_scope(scope: Optional[PackScope]) -> PackScope:
+    """Make `scope` (a closed one: its step's backward goes on with its images) the open scope again; None: a new scope of no owner."""
+    global _PACK_SCOPE
+    _PACK_SCOPE = scope if scope is not None else PackScope()
+    return _PACK_SCOPE
+
+
+def close_pack_scope(scope: Optional[PackScope] = None) -> None:
+    """No scope open any more; the scope's Parameter-sourced requests become the list the next scope of its owner and key starts from."""
+    global _PACK_SCOPE
+    scope = _PACK_SCOPE if scope is None else scope
+    if scope is not None and scope.plans is not None:
+        scope.plans[scope.plan_key] = list(scope.record.values())
+    _PACK_SCOPE = None
 
 
 def packed_weight(w: torch.Tensor, bias: Optional[torch.Tensor] = None, wt: bool = False, groups: int = 1,
                   split: bool = False, gemv: bool = False, mfma32: bool = False) -> torch.Tensor:
-    """tbx_pack_weight image of a LINEAR weight (+ bias). Cached on the weight's base tensor object (the nn.Parameter)
-    per view and version of both tensors: re-packed after an in-place update (optimizer step, load_state_dict), reused
-    otherwise - chains are rebuilt every eager step - and dropped with the parameter.
+    """tbx_pack_weight image of a LINEAR weight (+ bias), derived (_derived) from the views' places in their nn.Parameters: re-packed
+    after an in-place update or a move, reused otherwise (chains are rebuilt every eager step), per training step inside a PackScope.
     split=True: the tbx_pack_weight_split image (bf16 hi + lo halves) for stages flagged F_WSPLIT.
     gemv=True: the tbx_pack_weight_gemv image (column streams) for the F_WGEMV stages of live-row chains.
     mfma32=True: the tbx_pack_weight_mfma32 image (per-wave units of bf16 hi + lo fragments) for tbx_layer_tile."""
+    key = _pack_key(w, bias, wt, groups, split, gemv, mfma32)
+    scope = _PACK_SCOPE if mfma32 else None
+    if scope is not None and key not in scope.record:
+        wp, bp = _place(w), _place(bias)
+        if isinstance(wp[0], torch.nn.Parameter) and (bp is None or isinstance(bp[0], torch.nn.Parameter)):
+            scope.record[key] = (wp, bp, wt, groups)  # (open_pack_scope: next step's plan)
+    return _derived(key, (w, bias), _make_pack, key, scope, w, bias, wt, groups, split, gemv, mfma32)
+
+
+def _make_pack(key, scope, w, bias, wt, groups, split, gemv, mfma32):
+    # (the arguments are checked here: a hit is the same view of the same storage as when its image was made)
     assert w.is_cuda and w.dim() == 2 and w.stride(1) == 1 and w.dtype == torch.float32
-    cache, key, stamp = _pack_key(w, bias, wt, groups, split, gemv, mfma32)
-    if mfma32 and PACK_SCOPE is not None and "_record" in PACK_SCOPE:
-        base = w._base if w._base is not None else w
-        if isinstance(base, torch.nn.Parameter) and (bias is None or isinstance(bias if bias._base is None else bias._base, torch.nn.Parameter)):
-            PACK_SCOPE["_record"].setdefault(key, (w, bias, wt, groups))  # (open_pack_scope: next step's plan)
-    hit = cache.get(key)
-    if hit is not None and hit[0] == stamp:
-        return hit[1]
-    if mfma32 and PACK_SCOPE is not None:
-        grp = PACK_SCOPE.get("_groups", {}).get(id(w))
-        if grp is not None and any(r[0] is w and r[1] is bias and bool(r[2]) == bool(wt) and r[3] == groups for r in grp):
-            packed_weights_mfma32_multi(grp)  # pack_group: this request's image and its siblings' in one launch
-            return cache[key][1]
+    grp = None if scope is None else scope.groups.get(id(w))
+    if grp is not None and any(r[0] is w and r[1] is bias and bool(r[2]) == bool(wt) and r[3] == groups for r in grp):
+        packed_weights_mfma32_multi(grp)  # pack_group: this request's image and its siblings' in one launch
+        return _derived(key, (w, bias))
     n, k = (w.shape[1], w.shape[0] // groups) if wt else (w.shape[0] // groups, w.shape[1])
     if bias is not None:
         assert bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == groups * n
@@ -208,31 +274,25 @@ def packed_weight(w: torch.Tensor, bias: Optional[torch.Tensor] = None, wt: bool
     out = torch.empty(size, dtype=torch.float32, device=w.device)
     fn = lib.tbx_pack_weight_mfma32 if mfma32 else (lib.tbx_pack_weight_gemv if gemv else (lib.tbx_pack_weight_split if split else lib.tbx_pack_weight))
     _check(fn(_ptr(w), _ptr(bias), n, k, w.stride(0), groups, int(wt), _ptr(out), stream_ptr()), "tbx_pack_weight")
-    cache[key] = (stamp, out)
     return out
 
 
 def stacked_linear(linears, pad_out_to: int = 0):
     """(W [G * n, k], b [G * n]) = the weights / biases of G equally shaped nn.Linear layers stacked along the output dimension
     (each block zero-padded to pad_out_to output rows if given): branches that read the same input become ONE LINEAR stage
-    (G * n outputs), parallel branches one block-diagonal stage (groups = G). Cached like packed_weight: per parameter version,
-    or per training step inside PACK_SCOPE."""
-    ws, bs = [l.weight for l in linears], [l.bias for l in linears]
-    key = ("stacked", tuple(id(w) for w in ws), pad_out_to)
-    stamp = tuple((w._version, w.data_ptr(), b._version) for w, b in zip(ws, bs))
-    cache = PACK_SCOPE if PACK_SCOPE is not None else ws[0].__dict__.setdefault("_tbx_stacked", {})
-    hit = cache.get(key)
-    if hit is not None and hit[0] == stamp:
-        return hit[1], hit[2]
+    (G * n outputs), parallel branches one block-diagonal stage (groups = G). A derived image (_derived)."""
+    src = [l.weight for l in linears] + [l.bias for l in linears]
+    return _derived(("stacked", tuple(map(id, src)), pad_out_to), src, _make_stacked, src, pad_out_to)
+
+
+@torch.no_grad()
+def _make_stacked(src, pad_out_to):
+    ws, bs = src[:len(src) // 2], src[len(src) // 2:]
     n, k = ws[0].shape
     npad = max(n, pad_out_to)
-    with torch.no_grad():
-        W = torch.zeros(len(ws) * npad, k, dtype=torch.float32, device=ws[0].device)
-        B = torch.zeros(len(ws) * npad, dtype=torch.float32, device=ws[0].device)
-        for g, (w, b) in enumerate(zip(ws, bs)):
-            W[g * npad:g * npad + n].copy_(w)
-            B[g * npad:g * npad + n].copy_(b)
-    cache[key] = (stamp, W, B)
-    if PACK_SCOPE is not None:
-        PACK_SCOPE.setdefault("_keep", {})[id(ws[0])] = ws[0]
+    W = torch.zeros(len(ws) * npad, k, dtype=torch.float32, device=ws[0].device)
+    B = torch.zeros(len(ws) * npad, dtype=torch.float32, device=ws[0].device)
+    for g, (w, b) in enumerate(zip(ws, bs)):
+        W[g * npad:g * npad + n].copy_(w)
+        B[g * npad:g * npad + n].copy_(b)
     return W, B

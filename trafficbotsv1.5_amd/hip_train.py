@@ -9,7 +9,7 @@ import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
 from .abi import load  # noqa: F401
-from .hip_base import Seg, _check, _cptr, _drop_args, _ptr, packed_weight, stream_ptr
+from .hip_base import Seg, _check, _cptr, _derived, _drop_args, _name, _ptr, packed_weight, stream_ptr
 
 
 def keyed_dropout(x: torch.Tensor, p: float, seed: torch.Tensor, site: int, rows_per_scene: int, time_batch: int = 1,
@@ -33,30 +33,24 @@ def tall_linear_ok(x: torch.Tensor, k: int, n: int) -> bool:
 
 
 def _pad128(w: torch.Tensor, b: Optional[torch.Tensor]):
-    """(w, b) zero-padded to multiples of 128 in both dimensions (tbx_tall_linear's image for a 64-wide layer); cached like packed_weight:
-    per parameter version, or per training step inside PACK_SCOPE."""
-    from . import hip_base
-
+    """(w, b) zero-padded to multiples of 128 in both dimensions (tbx_tall_linear's image for a 64-wide layer); a derived image
+    (hip_base._derived: per weights version, or per training step inside a PackScope)."""
     n, k = w.shape
     npad, kpad = -(-n // 128) * 128, -(-k // 128) * 128
     if (npad, kpad) == (n, k):
         return w, b
-    key = ("pad128", id(w), None if b is None else id(b))
-    stamp = (w._version, w.data_ptr(), None if b is None else b._version)
-    cache = hip_base.PACK_SCOPE if hip_base.PACK_SCOPE is not None else w.__dict__.setdefault("_tbx_pad128", {})
-    hit = cache.get(key)
-    if hit is not None and hit[0] == stamp:
-        return hit[1], hit[2]
-    with torch.no_grad():
-        wp = torch.zeros(npad, kpad, dtype=torch.float32, device=w.device)
-        wp[:n, :k].copy_(w)
-        bp = None
-        if b is not None:
-            bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
-            bp[:n].copy_(b)
-    cache[key] = (stamp, wp, bp)
-    if hip_base.PACK_SCOPE is not None:
-        hip_base.PACK_SCOPE.setdefault("_keep", {})[id(w)] = w
+    return _derived(("pad128", _name(w), _name(b)), (w, b), _make_pad128, w, b, npad, kpad)
+
+
+@torch.no_grad()
+def _make_pad128(w, b, npad, kpad):
+    n, k = w.shape
+    wp = torch.zeros(npad, kpad, dtype=torch.float32, device=w.device)
+    wp[:n, :k].copy_(w)
+    bp = None
+    if b is not None:
+        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
+        bp[:n].copy_(b)
     return wp, bp
 
 

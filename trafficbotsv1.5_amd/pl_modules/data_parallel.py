@@ -149,6 +149,9 @@ class FlatAdamW:
             torch._fused_adamw_([self.p[a:b]], [self.grads.flat[a:b]], [self.m[a:b]], [self.v[a:b]], [], [self.steps[i0]], amsgrad=False,
                                 lr=float(g["lr"]), beta1=float(g["betas"][0]), beta2=float(g["betas"][1]), weight_decay=float(g["weight_decay"]),
                                 eps=float(g["eps"]), maximize=False, grad_scale=None, found_inf=None)
+        # the update went through the flat buffer, whose version counter is not the parameters': bump theirs as optimizer.step() does
+        # (hip_base.weights_stamp - derived weight images and rollout engines - must see the new weights)
+        torch.autograd.graph.increment_version(self.grads.params)
 
 
 def clip_gradients(params, max_norm: float):

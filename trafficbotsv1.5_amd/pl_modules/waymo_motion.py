@@ -17,6 +17,7 @@ from torch import Tensor, nn
 from .. import engine
 from ..config import AttrDict, to_attr
 from ..data_modules.scene_centric import SceneCentricPreProcessing
+from ..hip_base import weights_stamp
 from ..models.modules.distributions import MyDist
 from ..models.traffic_bots import TrafficBots
 from ..utils.buffer import RolloutBuffer
@@ -146,7 +147,7 @@ class WaymoMotion(LightningModule):
         sched = self.schedule if self.schedule is not None else engine.current()
         # (weights: every parameter's storage AND version - an optimizer step, load_state_dict, .to() or `p.data = ` all change one)
         key = (RolloutEngine.shape_key(**kw), dataclasses.astuple(sched), str(dev), self.training,
-               hash(tuple((p.data_ptr(), p._version) for p in self.model.parameters())))
+               hash(weights_stamp(self.model.parameters())))
         eng = self._engines.get(key) if self.engine_cache > 0 else None
         if eng is not None:
             eng.refill(**kw)

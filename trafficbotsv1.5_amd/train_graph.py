@@ -721,8 +721,7 @@ class backward_pack_scope:
     def __enter__(self):
         scope = getattr(self.wm, "_pack_scope", None)
         self.wm._pack_scope = None  # (one backward per scope: the optimizer step that follows ends the images' validity)
-        hip_base.PACK_SCOPE = scope if scope is not None else {}
-        return hip_base.PACK_SCOPE
+        return hip_base.reopen_pack_scope(scope)
 
     def __exit__(self, *exc):
         hip_base.close_pack_scope()
