@@ -1033,6 +1033,37 @@ int tbx_filter_futures(const uint8_t* flags, int col_bit, const uint8_t* ag_role
                        int t_start, float w_road_edge, int n_keep, float* score, int32_t* idx, const float* pred_pose,
                        float* trajs, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * WOMD modes of the joint futures. Replaces WOMDPostProcessing.forward (data_modules/womd_post_processing.py:37-72) with its
+ * default branches: softmax of the log-probabilities over the n_k futures of each agent (:55), reduction to k = min(n_k, k_pred)
+ * modes by traj_topk (:159-176) or - mtr_nms_thresh non-NULL - mtr_nms (:110-157), mpa_nms (:74-108) when mpa_nms_thresh is
+ * non-NULL, softmax(log(scores) / score_temperature) when score_temperature > 0 (:69-70), and the time samples
+ * sample_first : sample_end : sample_stride of the kept futures (:72; 4 : step_gt - step_current : 5, the 2 Hz samples). One
+ * launch, no host synchronisation. traj_aggr (:178-) is not implemented.
+ *   pred_pose [n_scene*n_k, n_ag, ld_t, 3] (x, y, yaw): the rollout log as the engine writes it; the futures are steps
+ *   [t_start, t_start + n_step) of it. log_prob [n_scene*n_k, n_ag] or NULL (zeros). ag_type [n_scene, n_ag, 3] u8.
+ *   mtr_nms_thresh / mpa_nms_thresh: HOST pointers to 3 floats (veh, ped, cyc; metres) or NULL (step off). The threshold of an
+ *   agent is sum_i type_i * thresh_i (0 for an agent without a type: nothing is within it). "Within": the mean over the n_step
+ *   steps of the xy distance (use_ade) or the distance at the last step, float32, summed in step order.
+ *   out_trajs [n_scene, n_ag, k, n_out, 3], n_out = ceil((sample_end - sample_first) / sample_stride); out_scores [n_scene, n_ag, k];
+ *   out_idx [n_scene, n_ag, k] i32 or NULL: the future each mode was taken from.
+ * Mode order (the reference's topk(sorted=False) leaves it unspecified): traj_topk in descending softmax score, ties to the lower
+ * future index; mtr_nms in pick order (first maximum on ties); n_k <= k_pred in future order.
+ * n_k <= 128, k_pred <= 8, n_step <= 91: anything else is TBX_ERR_UNSUPPORTED. */
+int tbx_womd_modes(const float* pred_pose, const float* log_prob, const uint8_t* ag_type, int n_scene, int n_k, int n_ag, int ld_t,
+                   int t_start, int n_step, int k_pred, int use_ade, const float* mtr_nms_thresh, const float* mpa_nms_thresh,
+                   float score_temperature, int sample_first, int sample_stride, int sample_end, float* out_trajs, float* out_scores,
+                   int32_t* out_idx, void* stream);
+
+/* Scenario frame -> global frame of WOSACPostProcessing.forward (data_modules/wosac_post_processing.py:69-79):
+ * utils/transform_utils.py:160-171 torch_pos2global, pos @ R(scenario_yaw)^T + scenario_center, and :216-226 torch_rad2global,
+ * (yaw + scenario_yaw + pi) % (2 pi) - pi with the sign of the divisor ([-pi, pi)). Points are n_scene * rows_per_scene rows of n_t
+ * steps, ld_t steps apart in the input: point (row, t) reads xy[(row * ld_t + t) * ld_xy + {0, 1}] and yaw[(row * ld_t + t) * ld_yaw].
+ *   scenario_center [n_scene, 2], scenario_yaw [n_scene]; out_pos [n_scene * rows_per_scene, n_t, 2], out_yaw [.., n_t] (dense) */
+int tbx_pose_to_global(const float* xy, int ld_xy, const float* yaw, int ld_yaw, const float* scenario_center,
+                       const float* scenario_yaw, int n_scene, int64_t rows_per_scene, int n_t, int ld_t, float* out_pos, float* out_yaw,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,10 @@ def default_sim_cfg(**overrides) -> AttrDict:
         optimizer=dict(lr=2e-4, weight_decay=1e-1, betas=(0.9, 0.95)),
         lr_navi=2e-4,
         lr_scheduler=dict(gamma=0.5, step_size=7),
+        womd_post_processing=dict(k_pred=6, use_ade=True, score_temperature=-1, mpa_nms_thresh=[2.0, 2.0, 2.0], mtr_nms_thresh=[],
+                                  aggr_thresh=[], n_iter_em=3),
+        wosac_post_processing=dict(step_gt=90, step_current=10, const_vel_z_sim=True, const_vel_no_sim=True, w_road_edge=0.0,
+                                   use_wosac_col=True),
     )
     cfg = to_attr(cfg)
     for k, v in overrides.items():

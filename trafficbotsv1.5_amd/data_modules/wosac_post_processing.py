@@ -3,8 +3,12 @@ futures simulated per scene keep the 32 with the fewest collisions / road-edge c
 role. The step right after the rollout and its rule checks; scoring, ranking and the gather of the
 kept trajectories are one C-ABI call (`tbx_filter_futures`) on the device-resident rollout log.
 
-The rest of the reference class (scenario-frame -> global-frame transform, protobuf submission) is out of scope.
+`forward` (:66-105) continues on the device: the kept futures and the not-simulated agents' histories are moved from the scenario
+frame to the global frame by `tbx_pose_to_global`; the records keep the reference's names and shapes. `get_scenario_rollouts` (protobuf)
+is out of scope.
 """
+from typing import Dict
+
 import torch
 from torch import Tensor, nn
 
@@ -40,5 +44,37 @@ class WOSACPostProcessing(nn.Module):
             float(self.w_road_edge), self.n_joint_future, pred_pose=buffer.pred_pose.reshape(n_sc * K, A, T, 3).float().contiguous())
         return trajs
 
-    def forward(self, batch, buffer: RolloutBuffer):
-        raise NotImplementedError("global-frame transform + WOSAC submission records are outside the hot path (SURVEY.md §8f)")
+    @torch.no_grad()
+    def forward(self, batch: Dict[str, Tensor], buffer: RolloutBuffer) -> Dict[str, Tensor]:
+        """wosac_post_processing.py:66-105. pos_sim / yaw_sim [n_sc, min(K, 32), n_ag, n_step_future, 2 / 1] and pos_no_sim / yaw_no_sim
+        [n_sc, n_ag_no_sim, n_step_history, 2 / 1] in the global frame, scenario_id [n_sc, 16] i32 (characters, padded with -1), the
+        other keys passed through."""
+        trajs = self._filter_futures(buffer, batch["ref/ag_role"])  # dense, or (K <= 32) a time slice of the log - read in place
+        n_sc, K, A, T = trajs.shape[:4]
+        ld_t = hip.log_row_steps(trajs)
+        if ld_t is None:
+            trajs, ld_t = trajs.float().contiguous(), T
+        center, yaw = batch["scenario_center"].float().contiguous(), batch["scenario_yaw"].float().contiguous()
+        pos_sim, yaw_sim = hip.pose_to_global(trajs, 3, trajs[..., 2], 3, center, yaw, K * A, T, ld_t)
+        pos_ns, yaw_ns = batch["history/agent_no_sim/pos"].float().contiguous(), batch["history/agent_no_sim/yaw_bbox"].float().contiguous()
+        N, Th = pos_ns.shape[1:3]
+        pos_no_sim, yaw_no_sim = hip.pose_to_global(pos_ns, pos_ns.shape[-1], yaw_ns, 1, center, yaw, N, Th, Th)
+        scenario_id = torch.full((n_sc, 16), -1, dtype=torch.int32)  # (wosac_post_processing.py:81-86; 16 = the longest id)
+        for i, str_id in enumerate(batch["scenario_id"]):
+            scenario_id[i, : len(str_id)] = torch.tensor([ord(c) for c in str_id], dtype=torch.int32)
+        return {
+            "scenario_id": scenario_id.to(trajs.device, non_blocking=True),
+            "valid_sim": batch["history/agent/valid"],
+            "pos_sim": pos_sim.view(n_sc, K, A, T, 2),
+            "z_sim": batch["history/agent/pos"][..., 2:3],
+            "yaw_sim": yaw_sim.view(n_sc, K, A, T, 1),
+            "valid_no_sim": batch["history/agent_no_sim/valid"],
+            "object_id_sim": batch["history/agent/object_id"],
+            "pos_no_sim": pos_no_sim.view(n_sc, N, Th, 2),
+            "z_no_sim": batch["history/agent_no_sim/pos"][..., 2:3],
+            "yaw_no_sim": yaw_no_sim.view(n_sc, N, Th, 1),
+            "object_id_no_sim": batch["history/agent_no_sim/object_id"],
+        }
+
+    def get_scenario_rollouts(self, wosac_data):
+        raise NotImplementedError("the protobuf submission records need waymo_open_dataset (SURVEY.md §8f)")

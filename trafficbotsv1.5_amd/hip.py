@@ -17,7 +17,7 @@ from .abi import HEADER_PATH, LIB_PATH, load  # noqa: F401
 from .hip_base import *  # noqa: F401,F403  (Seg, stream_ptr, packed_weight / stacked_linear / padded_weight)
 from .hip_base import _check, _cptr, _drop_args, _ptr  # noqa: F401
 from .hip_chain import *  # noqa: F401,F403  (Chain, group_tile_rows)
-from .hip_rules import *  # noqa: F401,F403  (rule_tables, rule_check, rule_accumulate, filter_futures)
+from .hip_rules import *  # noqa: F401,F403  (rule_tables, rule_check, rule_accumulate, filter_futures, womd_modes, pose_to_global)
 from .hip_train import *  # noqa: F401,F403  (the training entry points)
 from .hip_train import _drop6  # noqa: F401
 

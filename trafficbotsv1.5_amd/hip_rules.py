@@ -1,4 +1,5 @@
-"""ctypes wrappers of the rule-check / rollout-filter entry points (tbx_rule_*, tbx_filter_futures). Re-exported by hip.py."""
+"""ctypes wrappers of the rule-check / rollout-filter / post-processing entry points (tbx_rule_*, tbx_filter_futures, tbx_womd_modes,
+tbx_pose_to_global). Re-exported by hip.py."""
 import ctypes as C
 import os
 from typing import List, Optional, Sequence
@@ -82,3 +83,70 @@ def filter_futures(flags, col_bit: int, ag_role_any, n_scene: int, n_k: int, t_s
                                    stream_ptr())
     _check(rc, "tbx_filter_futures")
     return score, idx, trajs
+
+
+def _thresh3(thresh: Optional[Sequence[float]], what: str):
+    """[] / None -> NULL (the step is off), three floats (veh, ped, cyc) -> a host float[3]."""
+    if thresh is None or len(thresh) == 0:
+        return None
+    if len(thresh) != 3:
+        raise ValueError(f"{what}: expected [] or [veh, ped, cyc], got {len(thresh)} values")
+    return (C.c_float * 3)(*[float(v) for v in thresh])
+
+
+def log_row_steps(t) -> Optional[int]:
+    """t [..., A, T, 3] float32: a rollout log or a time slice of one (every dimension dense but for the row length)? -> the steps per
+    row of the underlying log, else None. Dimensions of size 1 carry no stride information and are not held against the view."""
+    if t.dtype != torch.float32 or t.shape[-1] != 3 or t.stride(-1) != 1 or t.stride(-2) != 3:
+        return None
+    lead = [(n, st) for n, st in zip(t.shape[:-2], t.stride()[:-2]) if n > 1]  # innermost last
+    if not lead:
+        return t.shape[-2]
+    ld3 = lead[-1][1] if t.shape[-3] > 1 else None  # stride of the agent dimension = 3 * steps per row
+    want = None
+    for n, st in reversed(lead):
+        if want is None:
+            if ld3 is None:  # one agent per row: the row length is whatever the next dimension's stride says
+                ld3 = st
+            want = st
+        if st != want or st % 3:
+            return None
+        want = st * n
+    return ld3 // 3 if ld3 // 3 >= t.shape[-2] else None
+
+
+def womd_modes(pred_pose, log_prob, ag_type_u8, n_scene: int, n_k: int, t_start: int, n_step: int, k_pred: int, use_ade: bool,
+               mtr_nms_thresh: Optional[Sequence[float]] = None, mpa_nms_thresh: Optional[Sequence[float]] = None,
+               score_temperature: float = -1.0, sample_first: int = 4, sample_stride: int = 5, sample_end: Optional[int] = None):
+    """tbx_womd_modes on the rollout log in place. pred_pose [n_scene*n_k, A, >= t_start + n_step, 3]: rows may be longer than what is
+    read (the engine's log, or a time slice of it - only the last two strides are fixed), log_prob [n_scene*n_k, A] or None,
+    ag_type_u8 [n_scene, A, 3] -> (trajs [n_scene, A, k, n_out, 3], scores [n_scene, A, k], idx [n_scene, A, k] i32)."""
+    R, A, T_avail = pred_pose.shape[:3]
+    ld_t = log_row_steps(pred_pose) if pred_pose.dim() == 4 else None
+    if ld_t is None or R != n_scene * n_k or t_start + n_step > T_avail:
+        raise RuntimeError("womd_modes: pred_pose must be [n_scene*n_k, A, T, 3] rows of the rollout log (dense but for the row length)")
+    mtr, mpa = _thresh3(mtr_nms_thresh, "mtr_nms_thresh"), _thresh3(mpa_nms_thresh, "mpa_nms_thresh")
+    sample_end = n_step if sample_end is None else min(sample_end, n_step)
+    k, n_out = min(n_k, k_pred), len(range(sample_first, sample_end, sample_stride))
+    dev = pred_pose.device
+    trajs = torch.empty(n_scene, A, k, n_out, 3, dtype=torch.float32, device=dev)
+    scores = torch.empty(n_scene, A, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(n_scene, A, k, dtype=torch.int32, device=dev)
+    rc = load().tbx_womd_modes(_ptr(pred_pose, torch.float32), _cptr(log_prob, torch.float32), _cptr(ag_type_u8, torch.uint8), n_scene, n_k,
+                               A, ld_t, t_start, n_step, k_pred, int(bool(use_ade)), mtr, mpa, float(score_temperature), sample_first,
+                               sample_stride, sample_end, _ptr(trajs), _ptr(scores), _ptr(idx), stream_ptr())
+    _check(rc, "tbx_womd_modes")
+    return trajs, scores, idx
+
+
+def pose_to_global(xy, ld_xy: int, yaw, ld_yaw: int, scenario_center, scenario_yaw, rows_per_scene: int, n_t: int, ld_t: int):
+    """tbx_pose_to_global: xy / yaw are tensors whose data pointers address point (row 0, step 0) -> (pos [n_scene*rows, n_t, 2],
+    yaw [n_scene*rows, n_t]) in the global frame."""
+    n_scene = scenario_yaw.shape[0]
+    pos = torch.empty(n_scene * rows_per_scene, n_t, 2, dtype=torch.float32, device=xy.device)
+    out_yaw = torch.empty(n_scene * rows_per_scene, n_t, dtype=torch.float32, device=xy.device)
+    rc = load().tbx_pose_to_global(_ptr(xy, torch.float32), ld_xy, _ptr(yaw, torch.float32), ld_yaw, _cptr(scenario_center, torch.float32),
+                                   _cptr(scenario_yaw, torch.float32), n_scene, rows_per_scene, n_t, ld_t, _ptr(pos), _ptr(out_yaw),
+                                   stream_ptr())
+    _check(rc, "tbx_pose_to_global")
+    return pos, out_yaw

@@ -3,7 +3,8 @@
 
 The rollout is a device-resident state machine (utils/rollout_engine.py) replaying one hipGraph per step; scenes and
 rollouts are independent, so multi-GPU inference shards them over ranks with no collective.
-WOMD / WOSAC metrics, submission writers and video logging of the reference are out of scope.
+`womd_post_processing` / `wosac_post_processing` (data_modules/) turn the rollout log into scored modes and global-frame records on the
+device; WOMD / WOSAC metrics, submission writers and video logging of the reference are out of scope.
 """
 import dataclasses
 from collections import OrderedDict
@@ -17,6 +18,8 @@ from torch import Tensor, nn
 from .. import engine
 from ..config import AttrDict, to_attr
 from ..data_modules.scene_centric import SceneCentricPreProcessing
+from ..data_modules.womd_post_processing import WOMDPostProcessing
+from ..data_modules.wosac_post_processing import WOSACPostProcessing
 from ..hip_base import weights_stamp
 from ..models.modules.distributions import MyDist
 from ..models.traffic_bots import TrafficBots
@@ -59,7 +62,8 @@ class WaymoMotion(LightningModule):
                  training_detach_model_input: bool, training_deterministic_action: bool, pred_navi_after_reached: bool,
                  differentiable_reward, dynamics, teacher_forcing_training, teacher_forcing_reactive_replay,
                  teacher_forcing_joint_future_pred, training_metrics, optimizer, lr_scheduler, lr_navi: float,
-                 n_joint_future_wosac: int = 32, joint_future_pred_deterministic_k0: bool = False, **unused) -> None:
+                 n_joint_future_wosac: int = 32, joint_future_pred_deterministic_k0: bool = False, womd_post_processing=None,
+                 wosac_post_processing=None, **unused) -> None:
         super().__init__()
         if pred_navi_after_reached:
             raise NotImplementedError("pred_navi_after_reached=False is the default (no per-step host branch)")
@@ -96,6 +100,12 @@ class WaymoMotion(LightningModule):
         self.teacher_forcing_training = TeacherForcing(**teacher_forcing_training)
         self.teacher_forcing_reactive_replay = TeacherForcing(**teacher_forcing_reactive_replay)
         self.teacher_forcing_joint_future_pred = TeacherForcing(**teacher_forcing_joint_future_pred)
+        # waymo_motion.py:99-110; a configuration without these sections builds neither module
+        if womd_post_processing:
+            self.womd_post_processing = WOMDPostProcessing(step_gt=time_step_gt, step_current=time_step_current,
+                                                           **_strip_target(womd_post_processing))
+        if wosac_post_processing:
+            self.wosac_post_processing = WOSACPostProcessing(**_strip_target(wosac_post_processing))
         self._engine: Optional[RolloutEngine] = None
         self._engines: "OrderedDict[tuple, RolloutEngine]" = OrderedDict()  # engines by (shapes, schedule, weights version): begin_rollout
         self.engine_cache = 2  # engines kept (least recently used dropped); 0: a fresh engine + graph capture per rollout

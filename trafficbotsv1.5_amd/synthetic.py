@@ -219,3 +219,49 @@ def make_filter_case(n_sc: int = 2, n_k: int = 48, n_ag: int = 12, n_step: int =
     first = lambda p: (torch.rand(n_sc, n_k, n_ag, n_step, generator=g) < p / n_step * 4).cummax(-1)[0]
     return {"pred_pose": torch.randn(n_sc, n_k, n_ag, n_step, 3, generator=g) * 30.0, "collided": first(p_col), "collided_wosac": first(p_col),
             "run_road_edge": first(p_edge), "ag_role": torch.rand(n_sc, n_ag, 3, generator=g) < 0.3}
+
+
+def make_womd_case(n_sc: int = 4, n_k: int = 32, n_ag: int = 64, n_step: int = 80, seed: int = 0, n_bundle: int = 5) -> Dict[str, torch.Tensor]:
+    """Seeded inputs of `WOMDPostProcessing.forward`: per agent the K futures fall into `n_bundle` speed x curvature bundles with
+    jitter (so that futures of a bundle lie within the NMS thresholds of each other and suppression actually happens), random
+    log-probabilities, random one-hot types and a few agents without a type (threshold 0: nothing is within it).
+    -> trajs [n_sc, K, A, T, 3] (x, y, yaw), log_prob [n_sc, K, A], ag_type [n_sc, A, 3] bool."""
+    g = torch.Generator().manual_seed(30_000 + seed)
+    spd = torch.rand(n_sc, 1, n_ag, 1, generator=g) * 12
+    mode = torch.randint(0, n_bundle, (n_sc, n_k, n_ag), generator=g).float()
+    t = torch.arange(1, n_step + 1, dtype=torch.float32).view(1, 1, 1, n_step) * 0.1
+    s = spd * (0.5 + 0.25 * mode)[..., None] * t
+    yaw = ((mode - (n_bundle - 1) / 2) * 0.004)[..., None] * s + 0.02 * torch.randn(n_sc, n_k, n_ag, 1, generator=g)
+    jit = torch.randn(n_sc, n_k, n_ag, 1, 2, generator=g) * 0.3 * t[..., None] / t.max()
+    trajs = torch.stack([s * torch.cos(yaw), s * torch.sin(yaw), yaw], -1)
+    trajs[..., :2] += jit
+    log_prob = torch.randn(n_sc, n_k, n_ag, generator=g) * 2
+    ag_type = torch.nn.functional.one_hot(torch.randint(0, 3, (n_sc, n_ag), generator=g), 3).bool()
+    ag_type[torch.rand(n_sc, n_ag, generator=g) < 0.05] = False
+    return {"trajs": trajs, "log_prob": log_prob, "ag_type": ag_type}
+
+
+def make_wosac_keys(n_sc: int = 1, n_ag: int = 64, seed: int = 0, n_ag_no_sim: int = 256, n_step_hist: int = 11) -> Dict[str, object]:
+    """The batch keys `WOSACPostProcessing.forward` reads besides those of `to_history_batch` (reference data_h5_womd.py:52-54 and
+    tensor_size_test): the scenario's global pose (a few km from the origin, as in WOMD) and id, and the agents that are not simulated.
+    `scenario_id` is a list of strings, as the reference's collate leaves it."""
+    g = torch.Generator().manual_seed(40_000 + seed)
+    U = lambda *s: torch.rand(*s, generator=g)
+    yaw0 = (U(n_sc, n_ag_no_sim, 1, 1) - 0.5) * 2 * math.pi
+    rate = (U(n_sc, n_ag_no_sim, 1, 1) - 0.5) * 0.4
+    t = torch.arange(n_step_hist, dtype=torch.float32).view(1, 1, n_step_hist, 1) * 0.1
+    pos0 = torch.cat([(U(n_sc, n_ag_no_sim, 1, 2) - 0.5) * 300.0, U(n_sc, n_ag_no_sim, 1, 1) * 3.0], -1)
+    vel = torch.cat([(U(n_sc, n_ag_no_sim, 1, 2) - 0.5) * 20.0, torch.zeros(n_sc, n_ag_no_sim, 1, 1)], -1)
+    ids = torch.stack([torch.randperm(4 * (n_ag + n_ag_no_sim), generator=g) for _ in range(n_sc)])
+    hexdigits = "0123456789abcdef"
+    return {
+        "scenario_center": (U(n_sc, 2) - 0.5) * 2.0e4,
+        "scenario_yaw": (U(n_sc) - 0.5) * 2 * math.pi,
+        "scenario_id": ["".join(hexdigits[int(c)] for c in torch.randint(0, 16, (int(n),), generator=g))
+                        for n in torch.randint(12, 17, (n_sc,), generator=g)],
+        "history/agent/object_id": ids[:, :n_ag].clone(),
+        "history/agent_no_sim/object_id": ids[:, n_ag : n_ag + n_ag_no_sim].clone(),
+        "history/agent_no_sim/valid": U(n_sc, n_ag_no_sim, n_step_hist) < 0.7,
+        "history/agent_no_sim/pos": pos0 + vel * t,
+        "history/agent_no_sim/yaw_bbox": yaw0 + rate * t,  # (not wrapped: some leave [-pi, pi) so that the transform's wrap is exercised)
+    }
