@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define TBX_ABI_VERSION 4
+#define TBX_ABI_VERSION 5
 
 enum {
   TBX_OK = 0,
@@ -97,74 +97,110 @@ int tbx_rel_pose_dense(const float* src_pose, const uint8_t* src_invalid, const 
                        int n_batch, int n_src, int n_tgt, int tgt_batch_div, float* rel_pose, float* rel_dist, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * K6: fused KNARPE attention (gather + relative-pose bias + ragged masked softmax + weighted sum).
- * Replaces modules/attention_rpe.py:137-190 (rpe branch, apply_q_rpe = False) in the exact factorised form
+ * K6: fused KNARPE attention (gather + relative-pose bias + ragged masked softmax + weighted sum), forward and backward.
+ * Replaces modules/attention_rpe.py:137-190 (rpe branch, apply_q_rpe = False) and its autograd in the exact factorised form
  *   score[h,t] = q_h . k_h[idx_t] + qt_h . e_t + qb_h          (qt_h = W_rpe_k,h^T q_h ; qb_h = q_h . b_rpe_k,h)
  *   out       = [ sum_t a[h,t] v_h[idx_t]  |  sum_t a[h,t] e_t  (one 128-vector per head) ]
  * with K/V projected BEFORE the gather (per-token tables), mask -> -inf, rows without any valid target un-masked and
  * flagged in `row_no_valid` (the caller zeroes their out-projection, attention_rpe.py:112-118,188-190), softmax of
  * score / sqrt(d_head). d_model = 128, n_head = 4, d_rpe = 128.
  *
- *   qbuf [n_batch*n_src, ldq]: q at q_off (128), qt at qt_off (4*128); rpe_k_bias [128] = linear_rpe.bias[0:128]
- *   (qb_h is formed in-kernel from q and rpe_k_bias)
- *   seg[i]: kv [n_batch/batch_div, n_tgt, ld_kv] with K at k_off and V at v_off; idx / invalid [n_batch, n_src, k];
- *           the pair's pose embedding either materialised (emb [n_batch, n_src, k, 128]) or as its relative pose
- *           (rel_pose [n_batch, n_src, k, 3] + freqs_xy / freqs_yaw = the `pose_rpe` buffers): then the kernel moves exactly
- *           the algorithmic K row + V row + 12 B + 4 B + 1 B per pair
- *   out  [n_batch*n_src, ldo >= 640]; row_no_valid [n_batch*n_src] u8
+ * One host-side argument struct, tbx_attn_t, and three entry points; each reads the fields listed for it and ignores the rest.
  * Limits: 1 <= n_seg <= 2, sum of k <= 128, 16-byte aligned rows.
  */
 typedef struct tbx_attn_seg {
-  const float* kv;
-  const int32_t* idx;
-  const uint8_t* invalid;
+  const float* kv;       /* [n_batch / batch_div, n_tgt, ld_kv] with K at k_off and V at v_off (128 channels each) */
+  const int32_t* idx;    /* [n_batch, n_src, k] the row's K nearest targets */
+  const uint8_t* invalid; /* [n_batch, n_src, k] */
   const float* emb;      /* [n_batch, n_src, k, 128] materialised pose embedding, or NULL */
-  const float* rel_pose; /* [n_batch, n_src, k, 3] relative pose (used when emb == NULL: the embedding is rebuilt in registers) */
+  const float* rel_pose; /* [n_batch, n_src, k, 3] relative pose (used when emb == NULL: the embedding is rebuilt in registers from
+                            freqs_xy / freqs_yaw, and the kernel moves exactly the algorithmic K row + V row + 12 B + 4 B + 1 B per pair) */
   int32_t ld_kv, k_off, v_off, n_tgt, batch_div, k;
   int32_t kv_bf16;       /* != 0: `kv` points to a bfloat16 table (ld_kv / k_off / v_off in elements): K and V rows move 2 B per
                             channel (529 B per pair instead of 1041), scores and sums accumulate in fp32. Forward only; every
                             segment of a call must use the same element type. */
 } tbx_attn_seg_t;
 
-int tbx_knarpe_attn_fwd(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                        int n_src, const tbx_attn_seg_t* segs /* host */, int n_seg, float* out, int ldo,
-                        uint8_t* row_no_valid, const float* freqs_xy /* [32] or NULL */, const float* freqs_yaw /* [64] or NULL */,
-                        void* stream);
+typedef struct tbx_attn_args {
+  /* query side (every entry point) */
+  const float* qbuf;        /* [n_batch*n_src, ldq]: q at q_off (128), qt at qt_off (4*128) */
+  const float* rpe_k_bias;  /* [128] = linear_rpe.bias[0:128]; qb_h is formed in-kernel from q and rpe_k_bias. Not read by _fwd_mfma
+                               (the constant q . b_rpe_k per head cancels in the softmax) */
+  const float* freqs_xy;    /* [32], freqs_yaw [64]: the `pose_rpe` buffers; required when a segment has emb == NULL */
+  const float* freqs_yaw;
+  tbx_attn_seg_t seg[2];    /* the targets, seg[0 .. n_seg) */
+  /* dropout on the attention probabilities (training; attention_rpe.py:171-172: on the softmax output, scaled by 1 / (1 - p)).
+   * p_drop = 0: none, drop_seed may be NULL; 0 <= p_drop < 1, time_batch >= 1 and time0 >= 0 always. The mask bit of (row, target slot,
+   * head) is a counter-based hash of the 64-bit seed at *drop_seed (DEVICE memory, read by the kernels) and of drop_call
+   * (distinguishes the calls of one training step): the backward regenerates the forward's mask from the same fields - whichever
+   * forward entry point ran - and a captured graph draws fresh masks when the host rewrites the seed between replays.
+   * Time-batched calls (training, train_graph.training_rollout_batched): the reference's training rollout detaches the policy inputs
+   * of every closed-loop step (waymo_motion.py:206-311 with training=True: the only cross-step gradient path is the dynamics chain),
+   * so once the states of the T steps are known the T policy evaluations of a scene are independent and are evaluated - and
+   * differentiated - as T consecutive batch entries: batch entry b is step time0 + b % time_batch of scene b / time_batch. The key is
+   * (seed, call, scene row, step, slot, head): the batched call draws exactly the masks of time_batch per-step calls made with
+   * (time_batch = 1, time0 = step). (1, 0): the key is (seed, call, row, slot, head). */
+  const uint64_t* drop_seed;
+  /* forward */
+  float* out;               /* [n_batch*n_src, ldo >= 640] (fold_image set: [n_batch*n_src, ldo >= 128], see below) */
+  uint8_t* row_no_valid;    /* [n_batch*n_src] u8 */
+  const float* fold_image;  /* tbx_knarpe_attn_fwd only; NULL: the 640-wide row. Set: the value half of `linear_rpe` is applied in the
+                               epilogue (attention_rpe.py:147,181-182: sum a (v + W_v e + b_v), softmax sums to 1):
+                                 out [n_batch*n_src, ldo >= 128] = (sum a v)_h + W_rpe_v,h (sum a e)_h + b_rpe_v,h  (zero rows where row_no_valid)
+                               fold_image = tbx_pack_weight_gemv(linear_rpe.weight[128:256], linear_rpe.bias[128:256], n = 32, k = 128,
+                               groups = 4): 66 KiB, fetched into LDS by LDS-DMA while the targets are swept. 128 floats per row leave the
+                               kernel instead of 640, and the grouped LINEAR stage that applied the fold in the following chain
+                               disappears; the result is bit-identical to that stage's (same fma order). Inference only: with
+                               p_drop > 0 the call returns TBX_ERR_UNSUPPORTED. */
+  /* backward (tbx_knarpe_attn_bwd). Probabilities are recomputed from the forward inputs; the pose embeddings carry no gradient
+   * (utils/rpe.py:7). */
+  const float* dout;        /* [n_batch*n_src, ldo >= 640] = d(sum a v) | d(sum a e per head) */
+  float* dqbuf;             /* [n_batch*n_src, ldq]: dq written at q_off, dqt at qt_off (other columns untouched) */
+  float* dkv[2];            /* dkv[i]: gradient of seg[i].kv, same shape / leading dimension. coef == NULL: dK, dV are ACCUMULATED with
+                               atomicAdd (zero it first). coef set: the K and V columns of every token row are OVERWRITTEN */
+  float* dbias_k;           /* [n_batch*n_src, 128]: per-row gradient of rpe_k_bias, overwritten (the parameter's gradient is the sum
+                               over rows: one shared 128-float accumulator serialises ~10^3-deep at the L2 atomic units). May be NULL:
+                               the gradient is identically zero in exact arithmetic - q_h . bk_h shifts all scores of a row, which
+                               its softmax ignores - and what the accumulation returns is round-off; the training step passes NULL
+                               and hands the parameter a zero gradient. */
+  /* The backward without dK / dV atomics (coef != NULL; 23 M float atomics per launch at 1024 rows x 89 pairs were 2/3 of the
+   * launch): the row kernel only stores 8 coefficients per pair into `coef` and a second kernel sums every target token's dK / dV
+   * row through the segment's inverse lists (tbx_knn_inverse, further down) - no pre-zeroing, no atomics. Then inv_ptr[i] and
+   * inv_list[i] are required for every segment, dkv[i] is 16-byte aligned, n_batch % seg[i].batch_div == 0 and n_tgt <= 2048. */
+  const int32_t* inv_ptr[2];
+  const int32_t* inv_list[2];
+  float* coef;              /* [n_batch*n_src, sum k, 8] scratch, or NULL: the atomics form */
+  int32_t ldq, q_off, qt_off, n_batch, n_src, n_seg;
+  int32_t ldo;              /* leading dimension of `out` (forward) / `dout` (backward) */
+  float p_drop;
+  uint32_t drop_call;
+  int32_t time_batch, time0, pad_;
+} tbx_attn_t;
+
+/* The fp32 forward (csrc/attn.hip). Reads the query side, dropout, out / ldo / row_no_valid / fold_image. A few hundred rows (the
+ * closed loop at one or a few scenes): 4 wavefronts share a row; large launches: a wavefront per row. fp32 or bfloat16 K/V tables
+ * (bfloat16: no dropout). */
+int tbx_knarpe_attn_fwd(const tbx_attn_t* args /* host */, void* stream);
 
 /* The forward of LARGE launches (a wavefront per source row) on the bf16 matrix cores (csrc/attn_mfma.hip): scores and
  * weighted sums as v_mfma_f32_16x16x32_bf16 products per source row (heads padded 4 -> 16), the pair's embedding evaluated in the
- * operand layout, V / embedding rows transposed through LDS (ds_read_b64_tr_b16), online softmax in fp32. Same arguments, `out`
- * layout and row_no_valid as tbx_knarpe_attn_fwd (every segment in the relative-pose form: emb == NULL; the constant q . b_rpe_k
- * per head cancels in the softmax and is not formed); fp32 or bfloat16 K/V tables. Operands are rounded to bfloat16 (q, qt, K, V,
- * e, softmax weights), accumulation and softmax in fp32: the bf16-ARITHMETIC schedule BASELINE configs[1] names (the reference runs
- * at precision 16, configs/trainer/default.yaml:16); tolerance in tests/test_hip_attn_mfma.py. A persistent launch (<= 2 workgroups
+ * operand layout, V / embedding rows transposed through LDS (ds_read_b64_tr_b16), online softmax in fp32. Reads the query side
+ * without rpe_k_bias, dropout, out / ldo (>= 640) / row_no_valid: the `out` layout, the flags and the dropout mask of
+ * tbx_knarpe_attn_fwd, so tbx_knarpe_attn_bwd regenerates exactly the mask this forward applied. Every segment in the relative-pose
+ * form (emb == NULL, freqs_* required), ld_kv / k_off / v_off multiples of 8, n_tgt * ld_kv * 4 < 2^32; fp32 or bfloat16 K/V tables.
+ * Operands are rounded to bfloat16 (q, qt, K, V, e, softmax weights), accumulation and softmax in fp32: the bf16-ARITHMETIC schedule
+ * BASELINE configs[1] names (the reference runs at precision 16, configs/trainer/default.yaml:16) and the forward of training's
+ * attention under the bf16-autocast-class arithmetic; tolerance in tests/test_hip_attn_mfma.py. A persistent launch (<= 3 workgroups
  * per CU) whose waves prefetch the next chunk's / the next row's gathers under the current chunk's arithmetic. */
-int tbx_knarpe_attn_fwd_mfma(const float* qbuf, int ldq, int q_off, int qt_off, int n_batch, int n_src,
-                             const tbx_attn_seg_t* segs /* host */, int n_seg, float* out, int ldo, uint8_t* row_no_valid,
-                             const float* freqs_xy /* [32] */, const float* freqs_yaw /* [64] */, void* stream);
-/* ... with dropout on the attention probabilities (training, attention_rpe.py:171-172) and time-batched keys: the arguments and the
- * mask of tbx_knarpe_attn_fwd_dropout_tb (below) - (seed, call, scene row, step, target slot, head) -, so the fp32 backward entry points
- * regenerate exactly the mask this forward applied. The forward of training's attention under the bf16-autocast-class arithmetic. */
-int tbx_knarpe_attn_fwd_mfma_dropout_tb(const float* qbuf, int ldq, int q_off, int qt_off, int n_batch, int n_src,
-                                        const tbx_attn_seg_t* segs /* host */, int n_seg, float* out, int ldo, uint8_t* row_no_valid,
-                                        const float* freqs_xy /* [32] */, const float* freqs_yaw /* [64] */, float p_drop,
-                                        const uint64_t* drop_seed /* device */, uint32_t drop_call, int time_batch, int time0,
-                                        void* stream);
+int tbx_knarpe_attn_fwd_mfma(const tbx_attn_t* args /* host */, void* stream);
 
-/* The forward for launches of a few hundred rows (the closed loop at one or a few scenes: 4 wavefronts share a row), with the
- * value half of `linear_rpe` applied in the epilogue (attention_rpe.py:147,181-182: sum a (v + W_v e + b_v), softmax sums to 1):
- *   out [n_batch*n_src, ldo >= 128] = (sum a v)_h + W_rpe_v,h (sum a e)_h + b_rpe_v,h   (zero rows where row_no_valid)
- * fold_image = tbx_pack_weight_gemv(linear_rpe.weight[128:256], linear_rpe.bias[128:256], n = 32, k = 128, groups = 4): 66 KiB,
- * fetched into LDS by LDS-DMA while the targets are swept. 128 floats per row leave the kernel instead of 640, and the grouped
- * LINEAR stage that applied the fold in the following chain disappears; the result is bit-identical to that stage's
- * (same fma order). Inference only (no dropout). */
-int tbx_knarpe_attn_fwd_folded(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch, int n_src,
-                               const tbx_attn_seg_t* segs /* host */, int n_seg, float* out, int ldo, uint8_t* row_no_valid,
-                               const float* freqs_xy, const float* freqs_yaw, const float* fold_image, void* stream);
+/* The backward of either forward (csrc/attn.hip; fp32 K/V tables only). Reads the query side, dropout, dout / ldo / dqbuf / dkv /
+ * dbias_k, and coef with the inverse lists (coef == NULL: the atomics form). */
+int tbx_knarpe_attn_bwd(const tbx_attn_t* args /* host */, void* stream);
 
 /* The attention half of a dec_cross_attn layer (transformer_rpe.py:207-233) as ONE launch, for launches of a few hundred rows
  * (one workgroup per row): folded self attention -> x += no valid target ? 0 : out_proj(.) -> LayerNorm_1 -> q = W_q . + b_q ->
- * W_rpe_k^T q per head -> folded cross attention. Replaces [tbx_knarpe_attn_fwd_folded, a row chain, tbx_knarpe_attn_fwd_folded];
+ * W_rpe_k^T q per head -> folded cross attention. Replaces [tbx_knarpe_attn_fwd with fold_image, a row chain, the same again];
  * results are bit-identical to those three launches. All *_image arguments are tbx_pack_weight_gemv images:
  *   fold_self_image / fold_cross_image: linear_rpe.weight[128:256], bias[128:256] of the two attention modules (n 32, k 128, groups 4)
  *   out_proj_image: the self attention's out_proj (n 128, k 128);  q_image: the cross attention's in_proj rows [0, 128) (n 128, k 128)
@@ -460,79 +496,17 @@ typedef struct tbx_pack_job {
 } tbx_pack_job_t;
 int tbx_pack_weight_mfma32_multi(const tbx_pack_job_t* jobs /* host */, int n_jobs, void* stream);
 
-/* Backward of tbx_knarpe_attn_fwd (training; autograd of modules/attention_rpe.py:137-190 in the factorised form).
- *   dout   [n_batch*n_src, ldo >= 640] = d(sum a v) | d(sum a e per head)
- *   dqbuf  [n_batch*n_src, ldq]  : dq written at q_off, dqt at qt_off (other columns untouched)
- *   dkv[i] : gradient of seg[i].kv, same shape / leading dimension; dK, dV are ACCUMULATED with atomicAdd (zero it first)
- *   dbias_k [n_batch*n_src, 128]: per-row gradient of rpe_k_bias, overwritten (the parameter's gradient is the sum over
- *   rows: one shared 128-float accumulator serialises ~10^3-deep at the L2 atomic units). May be NULL (every backward entry point):
- *   the gradient is identically zero in exact arithmetic - q_h . bk_h shifts all scores of a row, which its softmax ignores - and what
- *   the accumulation returns is round-off; the training step passes NULL and hands the parameter a zero gradient.
- * Probabilities are recomputed from the forward inputs; the pose embeddings carry no gradient (utils/rpe.py:7). */
-int tbx_knarpe_attn_bwd(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch, int n_src,
-                        const tbx_attn_seg_t* segs /* host */, int n_seg, const float* dout, int ldo, float* dqbuf,
-                        float* const* dkv /* host array of n_seg device pointers */, float* dbias_k,
-                        const float* freqs_xy, const float* freqs_yaw, void* stream);
-
-/* The same pair with attention-probability dropout (training; modules/attention_rpe.py:171-172: dropout on the softmax
- * output, scaled by 1 / (1 - p)). The mask bit of (row, target slot, head) is a counter-based hash of the 64-bit seed at
- * *drop_seed (DEVICE memory, read by the kernels) and of drop_call (distinguishes the calls of one training step), so
- * the backward regenerates the forward's mask from the same (seed, call) and a captured graph draws fresh masks when the
- * host rewrites the seed between replays. p_drop = 0 is exactly tbx_knarpe_attn_fwd / _bwd (drop_seed may be NULL). */
-int tbx_knarpe_attn_fwd_dropout(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                                int n_src, const tbx_attn_seg_t* segs /* host */, int n_seg, float* out, int ldo,
-                                uint8_t* row_no_valid, const float* freqs_xy, const float* freqs_yaw, float p_drop,
-                                const uint64_t* drop_seed /* device */, uint32_t drop_call, void* stream);
-int tbx_knarpe_attn_bwd_dropout(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                                int n_src, const tbx_attn_seg_t* segs /* host */, int n_seg, const float* dout, int ldo,
-                                float* dqbuf, float* const* dkv /* host array of n_seg device pointers */, float* dbias_k,
-                                const float* freqs_xy, const float* freqs_yaw, float p_drop,
-                                const uint64_t* drop_seed /* device */, uint32_t drop_call, void* stream);
-
-/* The backward without dK / dV atomics. tbx_knn_inverse turns a K-nearest set into per-table inverse lists (for every
- * target token the un-masked (source row, slot) pairs that selected it; pair id = row * k + slot; order unspecified):
+/* Inverse lists of a K-nearest set, for tbx_knarpe_attn_bwd's form without atomics (tbx_attn_t.coef): for every target token the
+ * un-masked (source row, slot) pairs that selected it; pair id = row * k + slot; order unspecified:
  *   inv_ptr [n_batch / tgt_batch_div, n_tgt + 1] i32 (offsets into the table's list), inv_list [n_tables, n_src * div * k] i32.
- * tbx_knarpe_attn_bwd_gather = tbx_knarpe_attn_bwd_dropout, but the row kernel only stores 8 coefficients per pair into
- * `coef` [n_batch*n_src, sum k, 8] (scratch) and a second kernel sums every target token's dK / dV row through the lists
- * (the K and V columns of every token row of dkv are OVERWRITTEN - no pre-zeroing, no atomics: 23 M float atomics per launch
- * at 1024 rows x 89 pairs were 2/3 of the launch).
  * n_tgt <= 2048. */
 int tbx_knn_inverse(const int32_t* idx, const uint8_t* invalid, int n_batch, int n_src, int k, int n_tgt, int tgt_batch_div,
                     int32_t* inv_ptr, int32_t* inv_list, void* stream);
-int tbx_knarpe_attn_bwd_gather(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                               int n_src, const tbx_attn_seg_t* segs /* host */, int n_seg, const float* dout, int ldo,
-                               float* dqbuf, float* const* dkv /* host array */, float* dbias_k, const float* freqs_xy,
-                               const float* freqs_yaw, float p_drop, const uint64_t* drop_seed /* device */, uint32_t drop_call,
-                               const int32_t* const* inv_ptr /* host array of n_seg device pointers */,
-                               const int32_t* const* inv_list /* host array */, float* coef, void* stream);
-
-/* Time-batched forms (training, train_graph.training_rollout_batched): the reference's training rollout detaches the policy
- * inputs of every closed-loop step (waymo_motion.py:206-311 with training=True: the only cross-step gradient path is the
- * dynamics chain), so once the states of the T steps are known the T policy evaluations of a scene are independent and are
- * evaluated - and differentiated - as T consecutive batch entries: batch entry b is step time0 + b % time_batch of scene
- * b / time_batch. The dropout mask is then keyed by (seed, call, scene row, step, slot, head): the batched call draws exactly
- * the masks of time_batch per-step calls made with (time_batch = 1, time0 = step). (1, 0) = the entry points above. */
-int tbx_knarpe_attn_fwd_dropout_tb(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                                   int n_src, const tbx_attn_seg_t* segs /* host */, int n_seg, float* out, int ldo,
-                                   uint8_t* row_no_valid, const float* freqs_xy, const float* freqs_yaw, float p_drop,
-                                   const uint64_t* drop_seed /* device */, uint32_t drop_call, int time_batch, int time0,
-                                   void* stream);
-int tbx_knarpe_attn_bwd_dropout_tb(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                                   int n_src, const tbx_attn_seg_t* segs /* host */, int n_seg, const float* dout, int ldo,
-                                   float* dqbuf, float* const* dkv /* host array */, float* dbias_k, const float* freqs_xy,
-                                   const float* freqs_yaw, float p_drop, const uint64_t* drop_seed /* device */,
-                                   uint32_t drop_call, int time_batch, int time0, void* stream);
-int tbx_knarpe_attn_bwd_gather_tb(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                                  int n_src, const tbx_attn_seg_t* segs /* host */, int n_seg, const float* dout, int ldo,
-                                  float* dqbuf, float* const* dkv /* host array */, float* dbias_k, const float* freqs_xy,
-                                  const float* freqs_yaw, float p_drop, const uint64_t* drop_seed /* device */,
-                                  uint32_t drop_call, int time_batch, int time0, const int32_t* const* inv_ptr /* host array */,
-                                  const int32_t* const* inv_list /* host array */, float* coef, void* stream);
 
 /* Elementwise dropout with the same kind of key (replaces F.dropout at modules/mlp.py:60-61, transformer_rpe.py:56-60,
  * 93-131 in training): y[row, c] = x[row, c] * keep / (1 - p), keep = hash(seed, site, step, scene row, c) >= p * 2^32.
  * x, y [rows, cols] contiguous (y may alias x); rows_per_scene rows per batch entry; batch entry b = row / rows_per_scene is
- * step time0 + b % time_batch of scene b / time_batch (see above), scene row = (b / time_batch) * rows_per_scene + row %
+ * step time0 + b % time_batch of scene b / time_batch (tbx_attn_t's time-batched calls), scene row = (b / time_batch) * rows_per_scene + row %
  * rows_per_scene. Its own backward (the gradient takes the same mask). `site` distinguishes the dropout sites of a step. */
 int tbx_keyed_dropout(const float* x, float* y, int64_t rows, int cols, int rows_per_scene, float p_drop,
                       const uint64_t* drop_seed /* device */, uint32_t site, int time_batch, int time0, void* stream);

@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol(hip):
                          "tbx_rowchain", "tbx_rowchain_ex", "tbx_knarpe_attn_bwd", "tbx_agent_prep", "tbx_tl_prep", "tbx_map_prep", "tbx_sim_step"}
     for s in syms:
         assert hasattr(lib, s), s
-    assert lib.tbx_version() == 4
+    assert lib.tbx_version() == 5
     assert lib.tbx_error_string(-2).decode().startswith("shape")
 
 
@@ -99,7 +99,7 @@ def test_ctypes_mirrors_have_the_layout_gcc_gives_the_header(hip, tmp_path):
     import subprocess
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    pairs = [("tbx_stage_t", hip.Stage), ("tbx_attn_seg_t", hip.AttnSeg), ("tbx_dec_mid_t", hip.DecMid), ("tbx_dec_layer_t", hip.DecLayer), ("tbx_heads_tail_t", hip.HeadsTail), ("tbx_knn_job_t", hip.KnnJob), ("tbx_pose_embed_job_t", hip.PoseEmbedJob), ("tbx_sim_state_t", hip.SimState),
+    pairs = [("tbx_stage_t", hip.Stage), ("tbx_attn_seg_t", hip.AttnSeg), ("tbx_attn_t", hip.Attn), ("tbx_dec_mid_t", hip.DecMid), ("tbx_dec_layer_t", hip.DecLayer), ("tbx_heads_tail_t", hip.HeadsTail), ("tbx_knn_job_t", hip.KnnJob), ("tbx_pose_embed_job_t", hip.PoseEmbedJob), ("tbx_sim_state_t", hip.SimState),
              ("tbx_train_chain_t", hip.TrainChainArgs), ("tbx_rule_ctx_t", hip.RuleCtx), ("tbx_layer_tile_t", hip.LayerTile),
              ("tbx_heads_tile_t", hip.HeadsTile), ("tbx_window_tile_t", hip.WindowTile), ("tbx_agent_prep_args_t", hip.AgentPrepArgs), ("tbx_front_t", hip.Front), ("tbx_tl_tail_t", hip.TlTail), ("tbx_pack_job_t", hip.PackJob)]
     src = tmp_path / "sz.c"
@@ -128,6 +128,81 @@ def test_new_entry_points_validate_arguments_without_a_gpu(hip):
     args.n_batch, args.n_ag, args.n_step, args.n_step_gt, args.n_node, args.window = 1, 4, 10, 11, 20, 11
     assert lib.tbx_train_chain_fwd(C.byref(args), None, 8, 0, 0, 1, None) == -1  # null state pointers
     assert lib.tbx_train_chain_bwd(C.byref(args), None, 8, 8, None, None, None) == -1
+
+
+def test_attention_entry_points_validate_their_argument_struct_without_a_gpu(hip):
+    """tbx_knarpe_attn_fwd / _fwd_mfma / _bwd on tbx_attn_t structs that must be refused BEFORE any launch (placeholder device
+    addresses, never dereferenced), with the codes the positional entry points gave for the same arguments: the checks of the query
+    side and the segments, the dropout fields, and what each entry point adds."""
+    lib = hip.load()
+    ARG, UNSUPPORTED, ALIGN = -1, -2, -3
+    dp = lambda i: 0x10000 * (i + 1)  # 16-byte aligned, distinct
+    fwd, mfma, bwd = lib.tbx_knarpe_attn_fwd, lib.tbx_knarpe_attn_fwd_mfma, lib.tbx_knarpe_attn_bwd
+
+    def args(**kw):  # a well-formed call of every entry point (relative-pose segments, the atomics backward), then the changes
+        a = hip.Attn(qbuf=dp(0), rpe_k_bias=dp(1), freqs_xy=dp(2), freqs_yaw=dp(3), out=dp(4), row_no_valid=dp(5), dout=dp(6), dqbuf=dp(7),
+                     dbias_k=dp(8), ldq=896, q_off=0, qt_off=128, n_batch=2, n_src=4, n_seg=2, ldo=640, time_batch=1)
+        for i, k in enumerate((24, 64)):
+            a.seg[i] = hip.AttnSeg(kv=dp(10 + i), idx=dp(12 + i), invalid=dp(14 + i), rel_pose=dp(16 + i), ld_kv=256, k_off=0, v_off=128,
+                                   n_tgt=100, batch_div=1, k=k)
+            a.dkv[i] = dp(18 + i)
+        for name, v in kw.items():
+            obj, _, field = name.rpartition("__")  # seg0__k -> a.seg[0].k
+            setattr(a.seg[int(obj[3:])] if obj else a, field, v)
+        return C.byref(a)
+
+    for f in (fwd, mfma, bwd):
+        assert f(None, None) == ARG
+        assert f(args(qbuf=None), None) == ARG
+        assert f(args(n_batch=0), None) == ARG
+        assert f(args(n_seg=3), None) == UNSUPPORTED
+        assert f(args(n_seg=0), None) == UNSUPPORTED
+        assert f(args(ldo=636), None) == UNSUPPORTED
+        assert f(args(seg0__k=65), None) == UNSUPPORTED          # 65 + 64 targets
+        assert f(args(ldq=898), None) == ALIGN
+        assert f(args(seg1__kv=None), None) == ARG
+        assert f(args(seg1__kv=dp(11) + 8), None) == ALIGN
+        assert f(args(seg1__kv_bf16=1), None) == UNSUPPORTED     # one element type per call
+        assert f(args(p_drop=1.0), None) == ARG
+        assert f(args(p_drop=-0.5), None) == ARG
+        assert f(args(time_batch=0), None) == ARG
+        assert f(args(time0=-1), None) == ARG
+        assert f(args(p_drop=0.1), None) == ARG                  # dropout without a seed
+        assert f(args(n_seg=3, qbuf=dp(0) + 4), None) == UNSUPPORTED  # (precedence: the shape before the alignment)
+    for f in (fwd, bwd):
+        assert f(args(rpe_k_bias=None), None) == ARG
+        assert f(args(freqs_xy=None), None) == ARG                # a relative-pose segment needs the frequencies
+        assert f(args(seg0__rel_pose=None), None) == ARG          # neither embedding nor relative pose
+        assert f(args(seg0__emb=dp(20) + 4), None) == ALIGN
+    # the forward entry points: outputs
+    for f in (fwd, mfma):
+        assert f(args(out=None), None) == ARG
+        assert f(args(row_no_valid=None), None) == ARG
+        assert f(args(out=dp(4) + 4), None) == ALIGN
+    assert fwd(args(out=dp(4) + 4, n_seg=3), None) == ALIGN       # the VALU forward looks at `out` first ...
+    assert mfma(args(out=dp(4) + 4, n_seg=3), None) == UNSUPPORTED  # ... the matrix-core forward at the shape
+    assert fwd(args(p_drop=0.1, drop_seed=dp(21), seg0__kv_bf16=1, seg1__kv_bf16=1), None) == UNSUPPORTED  # bf16 tables: no dropout
+    # the value fold: its own row width, and no dropout
+    assert fwd(args(fold_image=dp(22), ldo=128, p_drop=0.1, drop_seed=dp(21)), None) == UNSUPPORTED
+    assert fwd(args(fold_image=dp(22) + 4, ldo=128), None) == ALIGN
+    assert fwd(args(fold_image=dp(22), ldo=64), None) == ALIGN
+    assert fwd(args(fold_image=dp(22), ldo=128, n_seg=3), None) == UNSUPPORTED
+    # the matrix-core forward: relative-pose segments only, frequencies always, K/V columns in 8-element steps, 32-bit table offsets
+    assert mfma(args(seg0__emb=dp(20)), None) == UNSUPPORTED
+    assert mfma(args(seg0__emb=dp(20), seg0__rel_pose=None), None) == ARG
+    assert mfma(args(freqs_yaw=None, n_seg=3), None) == ARG
+    assert mfma(args(seg1__v_off=132), None) == ALIGN
+    assert mfma(args(seg0__n_tgt=1 << 22), None) == UNSUPPORTED
+    assert mfma(args(seg0__emb=dp(20), seg0__k_off=4), None) == UNSUPPORTED  # (precedence: the form before the alignment)
+    # the backward: gradients, fp32 tables only, the inverse lists of the form without atomics
+    assert bwd(args(dout=None), None) == ARG
+    assert bwd(args(dqbuf=dp(7) + 8), None) == ALIGN
+    assert bwd(args(seg0__kv_bf16=1, seg1__kv_bf16=1), None) == UNSUPPORTED
+    assert bwd(args(dkv=(C.c_void_p * 2)(dp(18), None)), None) == ARG
+    assert bwd(args(coef=dp(23)), None) == ARG                    # no inverse lists
+    assert bwd(args(coef=dp(23), inv_ptr=(C.c_void_p * 2)(dp(24), dp(25)), inv_list=(C.c_void_p * 2)(dp(26), None)), None) == ARG
+    assert bwd(args(coef=dp(23), inv_ptr=(C.c_void_p * 2)(dp(24), dp(25)), inv_list=(C.c_void_p * 2)(dp(26), dp(27)), n_batch=3, seg1__batch_div=2),
+               None) == ARG
 
 
 def test_group_tile_rows_picks_the_least_wasteful_tile(hip):

@@ -448,7 +448,7 @@ def test_live_row_chain_is_bit_identical_to_mfma_tiles(tb, live, rows):
 @pytest.mark.parametrize("S", [33, 1030])  # 1030: n * S >= 1024 rows -> the wave-per-row form (4 rows per workgroup, ragged tail)
 @pytest.mark.parametrize("bf16", [False, True])
 def test_folded_attention_epilogue_equals_the_fold_stage(tb, bf16, S):
-    """tbx_knarpe_attn_fwd_folded (the value half of linear_rpe applied in the attention kernel's epilogue, 128 floats per row
+    """tbx_knarpe_attn_fwd with fold_image (the value half of linear_rpe applied in the attention kernel's epilogue, 128 floats per row
     out) vs tbx_knarpe_attn_fwd's 640-wide row followed by the grouped LINEAR stage that applied the fold so far: bit-identical
     (same fma order), rows without a valid target flagged the same - for a one-segment and a two-segment call."""
     hip = import_module("trafficbots_amd.hip")

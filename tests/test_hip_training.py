@@ -315,7 +315,7 @@ def test_rollout_after_flat_adamw_steps_runs_on_the_trained_weights(tb):
 
 
 def test_attention_probability_dropout_vs_explicit_mask(tb):
-    """tbx_knarpe_attn_fwd_dropout / _bwd_dropout (attention_rpe.py:171-172 inside the kernels) against explicit torch math with
+    """tbx_knarpe_attn_fwd / _bwd with p_drop > 0 (attention_rpe.py:171-172 inside the kernels) against explicit torch math with
     the mask the (seed, call) pair produces (hip.dropout_keep_mask restates the kernels' counter hash): forward outputs and
     every gradient; two target segments so that the second segment's slots continue the first's."""
     dev = torch.device("cuda:0")
@@ -368,7 +368,7 @@ def test_attention_probability_dropout_vs_explicit_mask(tb):
     torch.testing.assert_close(out_h.detach().cpu(), out_c.detach(), rtol=2e-4, atol=2e-5)
     for a, b in zip(leaves_h, leaves_c):
         torch.testing.assert_close(a.grad.cpu(), b.grad, rtol=2e-3, atol=2e-4)
-    # the same backward through inverse K-nearest lists (tbx_knn_inverse + tbx_knarpe_attn_bwd_gather): no dK / dV atomics
+    # the same backward through inverse K-nearest lists (tbx_knn_inverse + tbx_knarpe_attn_bwd with coef): no dK / dV atomics
     lists = [hip.knn_inverse(meta[i][0], meta[i][1], (T1, T2)[i]) for i in range(2)]
     for i, (T, K) in enumerate(((T1, K1), (T2, K2))):  # the lists are the un-masked pairs grouped by target token
         ptr, lst = lists[i][0].cpu(), lists[i][1].cpu()
@@ -419,7 +419,7 @@ def test_keyed_dropout_time_batched_masks_equal_per_step_masks(tb):
 
 
 def test_attention_dropout_time_batched_call_equals_per_step_calls(tb):
-    """tbx_knarpe_attn_fwd_dropout_tb: one call over n x T entries (a scene's T steps consecutive, the scene's table shared
+    """tbx_knarpe_attn_fwd with time_batch = T: one call over n x T entries (a scene's T steps consecutive, the scene's table shared
     through batch_div = T) == T calls of n entries keyed (1, step), forward and backward."""
     dev = torch.device("cuda:0")
     TG = import_module("trafficbots_amd.train_graph")
@@ -1051,7 +1051,7 @@ def test_tall_linear_bf16_vs_float64(tb, m, k, n, wt, bias):
 
 
 def test_mfma_attention_forward_draws_the_valu_kernels_dropout_mask(tb):
-    """tbx_knarpe_attn_fwd_mfma_dropout_tb must drop exactly the (row, target slot, head) probabilities the VALU forward / backward kernels
+    """tbx_knarpe_attn_fwd_mfma with dropout must drop exactly the (row, target slot, head) probabilities the VALU forward / backward kernels
     drop for the same key (the fp32 backward regenerates the mask from it). V tables are one-hot rows - V[j][32 h + j] = 1 for every head
     h, K <= 32 distinct targets per row - so out[row][32 h + j] IS head h's dropped-and-rescaled probability of target j: the zero
     pattern of the two kernels must be identical (two segments, time-batched key), the kept probabilities agree to the bf16 operand

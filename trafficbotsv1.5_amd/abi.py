@@ -40,6 +40,15 @@ class AttnSeg(C.Structure):
         (n, C.c_int32) for n in ("ld_kv", "k_off", "v_off", "n_tgt", "batch_div", "k", "kv_bf16")]
 
 
+class Attn(C.Structure):
+    """tbx_attn_t (include/tbx_hip.h): the arguments of tbx_knarpe_attn_fwd / _fwd_mfma / _bwd."""
+    _fields_ = ([(n, C.c_void_p) for n in ("qbuf", "rpe_k_bias", "freqs_xy", "freqs_yaw")] + [("seg", AttnSeg * 2)]
+                + [(n, C.c_void_p) for n in ("drop_seed", "out", "row_no_valid", "fold_image", "dout", "dqbuf")]
+                + [("dkv", C.c_void_p * 2), ("dbias_k", C.c_void_p), ("inv_ptr", C.c_void_p * 2), ("inv_list", C.c_void_p * 2), ("coef", C.c_void_p)]
+                + [(n, C.c_int32) for n in ("ldq", "q_off", "qt_off", "n_batch", "n_src", "n_seg", "ldo")]
+                + [("p_drop", C.c_float), ("drop_call", C.c_uint32), ("time_batch", C.c_int32), ("time0", C.c_int32), ("pad_", C.c_int32)])
+
+
 class KnnJob(C.Structure):
     """tbx_knn_job_t (include/tbx_hip.h)."""
     _fields_ = ([(n, C.c_void_p) for n in ("src_pose", "src_invalid", "tgt_pose", "tgt_invalid", "idx", "invalid", "rel_pose", "emb")]
@@ -205,28 +214,13 @@ def load():
     lib.tbx_pose_embed.argtypes = [vp, i64, vp, vp, i32, vp, i32, i32, vp]
     lib.tbx_rel_pose_dense.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.tbx_diffbar_reward.argtypes = [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, vp]
-    lib.tbx_knarpe_attn_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp, vp, vp, vp]
-    lib.tbx_knarpe_attn_fwd_folded.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp, vp, vp, vp, vp]
-    lib.tbx_knarpe_attn_fwd_mfma.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp, vp, vp, vp]
-    lib.tbx_knarpe_attn_fwd_mfma_dropout_tb.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp, vp, vp, f32, vp, C.c_uint32,
-                                                        i32, i32, vp]
+    lib.tbx_knarpe_attn_fwd.argtypes = [C.POINTER(Attn), vp]
+    lib.tbx_knarpe_attn_fwd_mfma.argtypes = [C.POINTER(Attn), vp]
+    lib.tbx_knarpe_attn_bwd.argtypes = [C.POINTER(Attn), vp]
     lib.tbx_knarpe_dec_mid.argtypes = [C.POINTER(DecMid), vp]
     lib.tbx_knarpe_dec_layer.argtypes = [C.POINTER(DecLayer), vp]
     lib.tbx_knn_embed_multi.argtypes = [C.POINTER(KnnJob), i32, vp, vp, i32, vp]
     lib.tbx_knn_embed_multi_pe.argtypes = [C.POINTER(KnnJob), i32, vp, vp, i32, C.POINTER(PoseEmbedJob), vp]
-    lib.tbx_knarpe_attn_bwd.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp,
-                                        C.POINTER(C.c_void_p), vp, vp, vp, vp]
-    lib.tbx_knarpe_attn_fwd_dropout.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp, vp, vp,
-                                                f32, vp, C.c_uint32, vp]
-    lib.tbx_knarpe_attn_bwd_dropout.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp,
-                                                C.POINTER(C.c_void_p), vp, vp, vp, f32, vp, C.c_uint32, vp]
-    lib.tbx_knarpe_attn_fwd_dropout_tb.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp, vp, vp,
-                                                   f32, vp, C.c_uint32, i32, i32, vp]
-    lib.tbx_knarpe_attn_bwd_dropout_tb.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp,
-                                                   C.POINTER(C.c_void_p), vp, vp, vp, f32, vp, C.c_uint32, i32, i32, vp]
-    lib.tbx_knarpe_attn_bwd_gather_tb.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp,
-                                                  C.POINTER(C.c_void_p), vp, vp, vp, f32, vp, C.c_uint32, i32, i32,
-                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp]
     lib.tbx_keyed_dropout.argtypes = [vp, vp, i64, i32, i32, f32, vp, C.c_uint32, i32, i32, vp]
     lib.tbx_linear_wgrad_splits.argtypes = [i64, i32, i32]
     lib.tbx_linear_wgrad.argtypes = [vp, i32, vp, i32, i64, i32, i32, vp, vp, vp, i32, vp]
@@ -248,9 +242,6 @@ def load():
     lib.tbx_train_chain_fwd_windows.argtypes = [C.POINTER(TrainChainArgs), vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.tbx_train_chain_bwd.argtypes = [C.POINTER(TrainChainArgs), vp, i64, i64, vp, vp, vp]
     lib.tbx_knn_inverse.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.tbx_knarpe_attn_bwd_gather.argtypes = [vp, i32, i32, i32, vp, i32, i32, C.POINTER(AttnSeg), i32, vp, i32, vp,
-                                               C.POINTER(C.c_void_p), vp, vp, vp, f32, vp, C.c_uint32, C.POINTER(C.c_void_p),
-                                               C.POINTER(C.c_void_p), vp, vp]
     lib.tbx_pack_weight_size.argtypes = [i32, i32, i32]
     lib.tbx_pack_weight_size.restype = C.c_int64
     lib.tbx_pack_weight.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
@@ -301,11 +292,11 @@ def load():
     lib.tbx_attn_fold_fwd.argtypes = [vp] * 14
     lib.tbx_attn_fold_bwd.argtypes = [vp] * 19
     lib.tbx_rule_navi_check.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    for name in ("tbx_layer_tile", "tbx_heads_tile", "tbx_window_tile", "tbx_front", "tbx_tall_linear", "tbx_pack_weight_mfma32", "tbx_pack_weight_mfma32_multi", "tbx_pack_weight", "tbx_pack_weight_split", "tbx_pack_weight_gemv", "tbx_rowchain_live", "tbx_knarpe_attn_fwd_folded", "tbx_knarpe_dec_mid", "tbx_knarpe_dec_layer", "tbx_knn_embed_multi", "tbx_knn_embed_multi_pe", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd", "tbx_knarpe_attn_bwd", "tbx_knarpe_attn_fwd_dropout", "tbx_knarpe_attn_bwd_dropout", "tbx_knarpe_attn_bwd_gather", "tbx_knarpe_attn_fwd_dropout_tb", "tbx_knarpe_attn_bwd_dropout_tb", "tbx_knarpe_attn_bwd_gather_tb", "tbx_keyed_dropout", "tbx_linear_wgrad_splits", "tbx_linear_wgrad", "tbx_linear_wgrad_bf16", "tbx_tall_linear_bf16", "tbx_tl_tail_tile", "tbx_tl_tail_tile_bf16", "tbx_tall_linear_dual", "tbx_tall_linear_dual_bf16", "tbx_layernorm_fwd", "tbx_layernorm_bwd_partials", "tbx_layernorm_bwd", "tbx_layernorm_bwd_add", "tbx_residual_drop_fwd", "tbx_residual_drop_bwd", "tbx_relu_drop_fwd", "tbx_relu_drop_bwd", "tbx_pair_bias_relu", "tbx_pointnet_tail_fwd", "tbx_pointnet_tail_bwd", "tbx_masked_maxpool_fwd", "tbx_masked_maxpool_bwd", "tbx_train_chain_fwd", "tbx_train_chain_fwd_windows", "tbx_train_chain_bwd", "tbx_knn_inverse", "tbx_rowchain", "tbx_rowchain_ex", "tbx_agent_prep", "tbx_tl_prep",
+    for name in ("tbx_layer_tile", "tbx_heads_tile", "tbx_window_tile", "tbx_front", "tbx_tall_linear", "tbx_pack_weight_mfma32", "tbx_pack_weight_mfma32_multi", "tbx_pack_weight", "tbx_pack_weight_split", "tbx_pack_weight_gemv", "tbx_rowchain_live", "tbx_knarpe_dec_mid", "tbx_knarpe_dec_layer", "tbx_knn_embed_multi", "tbx_knn_embed_multi_pe", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd", "tbx_knarpe_attn_bwd", "tbx_keyed_dropout", "tbx_linear_wgrad_splits", "tbx_linear_wgrad", "tbx_linear_wgrad_bf16", "tbx_tall_linear_bf16", "tbx_tl_tail_tile", "tbx_tl_tail_tile_bf16", "tbx_tall_linear_dual", "tbx_tall_linear_dual_bf16", "tbx_layernorm_fwd", "tbx_layernorm_bwd_partials", "tbx_layernorm_bwd", "tbx_layernorm_bwd_add", "tbx_residual_drop_fwd", "tbx_residual_drop_bwd", "tbx_relu_drop_fwd", "tbx_relu_drop_bwd", "tbx_pair_bias_relu", "tbx_pointnet_tail_fwd", "tbx_pointnet_tail_bwd", "tbx_masked_maxpool_fwd", "tbx_masked_maxpool_bwd", "tbx_train_chain_fwd", "tbx_train_chain_fwd_windows", "tbx_train_chain_bwd", "tbx_knn_inverse", "tbx_rowchain", "tbx_rowchain_ex", "tbx_agent_prep", "tbx_tl_prep",
                  "tbx_map_prep", "tbx_sim_step", "tbx_sim_step_parts", "tbx_sim_step_tl_prep", "tbx_rule_tables", "tbx_rule_grid", "tbx_rule_grid_cells", "tbx_rule_check", "tbx_rule_accumulate", "tbx_filter_futures", "tbx_rule_navi_check", "tbx_attn_fold_fwd", "tbx_attn_fold_bwd", "tbx_tall_linear_relu_drop", "tbx_tall_linear_relu_drop_bf16", "tbx_front_pair", "tbx_knarpe_dec_layer_pair",
-                 "tbx_womd_modes", "tbx_pose_to_global", "tbx_rel_pose_dense", "tbx_diffbar_reward", "tbx_knarpe_attn_fwd_mfma", "tbx_knarpe_attn_fwd_mfma_dropout_tb"):
+                 "tbx_womd_modes", "tbx_pose_to_global", "tbx_rel_pose_dense", "tbx_diffbar_reward", "tbx_knarpe_attn_fwd_mfma"):
         getattr(lib, name).restype = C.c_int
-    if lib.tbx_version() != 4:
+    if lib.tbx_version() != 5:
         raise ImportError("libtbx_hip.so ABI version mismatch")
     # (an entry point without argtypes would get 64-bit handles - stream pointers under graph capture - as C ints)
     untyped = [s for s in declared_symbols() if getattr(lib, s).argtypes is None and s not in ("tbx_error_string", "tbx_version")]

@@ -21,6 +21,7 @@
 
 #include "../../include/tbx_hip.h"
 #include "attn_core.h"
+#include "attn_host.h"
 #include "tbx_common.h"
 
 #ifdef TBX_ATTN_CLOCK
@@ -60,7 +61,7 @@ struct AttnArgs {
   // b is step drop_time0 + b % T of scene b / T, and the mask is keyed by (scene row, step) - the masks of the batched call
   // are exactly those of T per-step calls with (T = 1, time0 = step). T = 1, time0 = 0: the plain (row) key.
   int drop_time_batch, drop_time0;
-  // tbx_knarpe_attn_fwd_folded: the tbx_pack_weight_gemv image of linear_rpe's value half (4 groups x 32 outputs, k = 128):
+  // tbx_attn_t.fold_image: the tbx_pack_weight_gemv image of linear_rpe's value half (4 groups x 32 outputs, k = 128):
   // the epilogue then forms (sum a v)_h + W_rpe_v,h (sum a e)_h + b_rpe_v,h itself and stores 128 floats per row instead of 640
   const float* fold_img;
   // wave-per-row form: the 4 rows of a workgroup are the SAME source token in 4 consecutive batch entries (row = (4*(quad / n_src)
@@ -791,69 +792,29 @@ static int attn_xcd_mask() {
 }
 static int attn_xcd() { return attn_xcd_mask() & 1; }
 
-int fill_args(AttnArgs& a, const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch, int n_src,
-              const tbx_attn_seg_t* segs, int n_seg, int ldo, const float* fxy, const float* fyaw) {
-  if (!qbuf || !rpe_k_bias || !segs || n_batch <= 0 || n_src <= 0) return TBX_ERR_ARG;
-  if (n_seg < 1 || n_seg > 2 || ldo < D + NH * DR) return TBX_ERR_UNSUPPORTED;
-  if ((ldq % 4) || (q_off % 4) || (qt_off % 4) || (ldo % 4) || (((uintptr_t)qbuf) & 15) || (((uintptr_t)rpe_k_bias) & 15))
-    return TBX_ERR_ALIGN;
-  int ktot = 0;
-  for (int i = 0; i < n_seg; ++i) {
-    const tbx_attn_seg_t& s = segs[i];
-    if (!s.kv || !s.idx || !s.invalid || (!s.emb && !s.rel_pose) || s.k <= 0 || s.n_tgt <= 0 || s.batch_div <= 0) return TBX_ERR_ARG;
-    if (!s.emb && (!fxy || !fyaw)) return TBX_ERR_ARG;
-    if ((s.ld_kv % 4) || (s.k_off % 4) || (s.v_off % 4) || (((uintptr_t)s.kv) & 15) || (s.emb && (((uintptr_t)s.emb) & 15)))
-      return TBX_ERR_ALIGN;
-    if ((s.kv_bf16 != 0) != (segs[0].kv_bf16 != 0)) return TBX_ERR_UNSUPPORTED;  // one element type per call
-    ktot += s.k;
-    a.seg[i] = s;
-  }
-  if (n_seg == 1) a.seg[1] = a.seg[0];
-  if (ktot > KMAX) return TBX_ERR_UNSUPPORTED;
-  a.qbuf = qbuf;
-  a.rpe_k_bias = rpe_k_bias;
-  a.fxy = fxy;
-  a.fyaw = fyaw;
+// AttnArgs of a call: the shared checks and fields (attn_host.h) + what only these kernels take; then the dropout fields.
+int fill_args(AttnArgs& a, const tbx_attn_t& t, int ldo) {
+  const int rc = fill_common(a, t, ldo, false);
+  if (rc != TBX_OK) return rc;
+  a.rpe_k_bias = t.rpe_k_bias;
   a.out = nullptr;
   a.row_no_valid = nullptr;
-  a.ldq = ldq;
-  a.q_off = q_off;
-  a.qt_off = qt_off;
-  a.ldo = ldo;
-  a.n_rows = n_batch * n_src;
-  a.n_src = n_src;
-  a.n_seg = n_seg;
   a.scale = 1.0f / sqrtf((float)DH);
-  a.scale2 = 1.4426950408889634f / sqrtf((float)DH);
   a.fold_img = nullptr;
   static const bool bm_env = [] { const char* e = getenv("TBX_ATTN_BATCH_MAJOR"); return !(e && e[0] == '0'); }();
   bool shared = false;
-  for (int i = 0; i < n_seg; ++i) shared = shared || segs[i].batch_div > 1;
-  a.batch_major = (bm_env && shared && n_batch % 4 == 0) ? 1 : 0;
-  a.xcd = attn_xcd();  // (set_dropout clears it for training's launches)
+  for (int i = 0; i < t.n_seg; ++i) shared = shared || t.seg[i].batch_div > 1;
+  a.batch_major = (bm_env && shared && t.n_batch % 4 == 0) ? 1 : 0;
+  a.xcd = attn_xcd();  // (set_drop clears it for training's launches)
   return TBX_OK;
 }
 
-}  // namespace
-
-namespace {
-int set_dropout(AttnArgs& a, float p_drop, const uint64_t* drop_seed, uint32_t drop_call, int time_batch, int time0) {
-  a.drop_seed = drop_seed;
-  a.drop_call = drop_call;
-  a.drop_thresh = 0u;
-  a.drop_scale = 1.f;
-  a.drop_time_batch = time_batch;
-  a.drop_time0 = time0;
-  if (p_drop < 0.f || p_drop >= 1.f || time_batch < 1 || time0 < 0) return TBX_ERR_ARG;
-  if (p_drop > 0.f) {
-    if (!drop_seed) return TBX_ERR_ARG;
-    const double th = (double)p_drop * 4294967296.0;
-    a.drop_thresh = th < 1.0 ? 1u : (uint32_t)th;
-    a.drop_scale = 1.0f / (1.0f - p_drop);
-    if (!(attn_xcd_mask() & 8)) a.xcd = 0;  // (training's launches: the plain order - see attn_xcd_mask; bit 3 forces it on)
-  }
-  return TBX_OK;
+int set_drop(AttnArgs& a, const tbx_attn_t& t) {
+  const int rc = set_dropout(a, t);
+  if (rc == TBX_OK && a.drop_thresh != 0u && !(attn_xcd_mask() & 8)) a.xcd = 0;  // (training's launches: the plain order - see attn_xcd_mask; bit 3 forces it on)
+  return rc;
 }
+
 }  // namespace
 
 static int fold_grid_max() {  // 2 workgroups (78 KiB of LDS each) per CU
@@ -885,23 +846,12 @@ static int attn_big_rows(bool dropout = true) {
   return dropout ? big_rows : big_rows_infer;
 }
 
-extern "C" int tbx_knarpe_attn_fwd_dropout_tb(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias,
-                                              int n_batch, int n_src, const tbx_attn_seg_t* segs, int n_seg, float* out, int ldo,
-                                              uint8_t* row_no_valid, const float* freqs_xy, const float* freqs_yaw, float p_drop,
-                                              const uint64_t* drop_seed, uint32_t drop_call, int time_batch, int time0,
-                                              void* stream) {
-  if (!out || !row_no_valid) return TBX_ERR_ARG;
-  if (((uintptr_t)out) & 15) return TBX_ERR_ALIGN;
-  AttnArgs a;
-  int rc = fill_args(a, qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, ldo, freqs_xy, freqs_yaw);
-  if (rc != TBX_OK) return rc;
-  rc = set_dropout(a, p_drop, drop_seed, drop_call, time_batch, time0);
-  if (rc != TBX_OK) return rc;
-  a.out = out;
-  a.row_no_valid = row_no_valid;
+// the 640-wide row (t.fold_image == NULL), with or without dropout
+static int launch_fwd(AttnArgs& a, const tbx_attn_t& t, hipStream_t hs) {
+  const tbx_attn_seg_t* segs = t.seg;
+  const int n_seg = t.n_seg;
   const bool big = a.n_rows >= attn_big_rows(a.drop_thresh != 0u);  // a wave per row from here on (below: 4 waves split a row's targets)
   const dim3 grid(big ? (a.n_rows + 3) / 4 : a.n_rows), block(256);
-  hipStream_t hs = (hipStream_t)stream;
   // the LDS-ring form (opt-in, TBX_ATTN_RING=1 / 2): large launches without dropout whose segments are all given as relative poses
   static const int ring_mode = [] { const char* e = getenv("TBX_ATTN_RING"); return e ? atoi(e) : 0; }();  // measured: no gain, opt-in
   // ... and, by default, launches that leave every SIMD with at most ONE wave (<= 1024 rows a wave per row: training's stepping pass,
@@ -954,25 +904,15 @@ extern "C" int tbx_knarpe_attn_fwd_dropout_tb(const float* qbuf, int ldq, int q_
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 
-extern "C" int tbx_knarpe_attn_fwd_folded(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                                          int n_src, const tbx_attn_seg_t* segs, int n_seg, float* out, int ldo, uint8_t* row_no_valid,
-                                          const float* freqs_xy, const float* freqs_yaw, const float* fold_image, void* stream) {
-  if (!out || !row_no_valid || !fold_image) return TBX_ERR_ARG;
-  if ((((uintptr_t)out) & 15) || (((uintptr_t)fold_image) & 15) || (ldo & 3) || ldo < D) return TBX_ERR_ALIGN;
-  AttnArgs a;
-  int rc = fill_args(a, qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, D + NH * DR, freqs_xy, freqs_yaw);
-  if (rc != TBX_OK) return rc;
-  rc = set_dropout(a, 0.f, nullptr, 0u, 1, 0);
-  if (rc != TBX_OK) return rc;
-  a.ldo = ldo;
-  a.out = out;
-  a.row_no_valid = row_no_valid;
-  a.fold_img = fold_image;
+// the value fold in the epilogue (t.fold_image): 128 floats per row, inference only
+static int launch_fwd_folded(AttnArgs& a, const tbx_attn_t& t, hipStream_t hs) {
+  if (a.drop_thresh != 0u) return TBX_ERR_UNSUPPORTED;
+  a.ldo = t.ldo;
+  a.fold_img = t.fold_image;
   const bool big = a.n_rows >= attn_big_rows();  // a wave per row from here on, 4 rows per workgroup
   const int quads = (a.n_rows + 3) / 4;
   const dim3 grid(big ? (quads < fold_grid_max() ? quads : fold_grid_max()) : a.n_rows), block(256);
-  hipStream_t hs = (hipStream_t)stream;
-  if (segs[0].kv_bf16 != 0) {
+  if (t.seg[0].kv_bf16 != 0) {
     if (big)
       hipLaunchKernelGGL((knarpe_attn_kernel<1, false, true, true>), grid, block, 0, hs, a);
     else
@@ -986,66 +926,59 @@ extern "C" int tbx_knarpe_attn_fwd_folded(const float* qbuf, int ldq, int q_off,
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 
-extern "C" int tbx_knarpe_attn_fwd(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                                   int n_src, const tbx_attn_seg_t* segs, int n_seg, float* out, int ldo,
-                                   uint8_t* row_no_valid, const float* freqs_xy, const float* freqs_yaw, void* stream) {
-  return tbx_knarpe_attn_fwd_dropout_tb(qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, out, ldo, row_no_valid,
-                                        freqs_xy, freqs_yaw, 0.f, nullptr, 0u, 1, 0, stream);
+extern "C" int tbx_knarpe_attn_fwd(const tbx_attn_t* t, void* stream) {
+  if (!t || !t->out || !t->row_no_valid) return TBX_ERR_ARG;
+  const bool fold = t->fold_image != nullptr;
+  if ((((uintptr_t)t->out) & 15) || (fold && ((((uintptr_t)t->fold_image) & 15) || (t->ldo & 3) || t->ldo < D))) return TBX_ERR_ALIGN;
+  AttnArgs a;
+  int rc = fill_args(a, *t, fold ? D + NH * DR : t->ldo);  // (the folded row's own width was checked above)
+  if (rc != TBX_OK) return rc;
+  rc = set_drop(a, *t);
+  if (rc != TBX_OK) return rc;
+  a.out = t->out;
+  a.row_no_valid = t->row_no_valid;
+  return fold ? launch_fwd_folded(a, *t, (hipStream_t)stream) : launch_fwd(a, *t, (hipStream_t)stream);
 }
 
-extern "C" int tbx_knarpe_attn_bwd_dropout_tb(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias,
-                                              int n_batch, int n_src, const tbx_attn_seg_t* segs, int n_seg, const float* dout,
-                                              int ldo, float* dqbuf, float* const* dkv, float* dbias_k, const float* freqs_xy,
-                                              const float* freqs_yaw, float p_drop, const uint64_t* drop_seed, uint32_t drop_call,
-                                              int time_batch, int time0, void* stream) {
-  if (!dout || !dqbuf || !dkv) return TBX_ERR_ARG;  // (dbias_k may be NULL: not computed)
-  if ((((uintptr_t)dout) & 15) || (((uintptr_t)dqbuf) & 15)) return TBX_ERR_ALIGN;
+extern "C" int tbx_knarpe_attn_bwd(const tbx_attn_t* t, void* stream) {
+  if (!t || !t->dout || !t->dqbuf) return TBX_ERR_ARG;  // (dbias_k may be NULL: not computed)
+  if ((((uintptr_t)t->dout) & 15) || (((uintptr_t)t->dqbuf) & 15)) return TBX_ERR_ALIGN;
   AttnBwdArgs b;
-  int rc = fill_args(b.f, qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, ldo, freqs_xy, freqs_yaw);
+  int rc = fill_args(b.f, *t, t->ldo);
   if (rc != TBX_OK) return rc;
+  const tbx_attn_seg_t* segs = t->seg;
+  const int n_seg = t->n_seg, n_batch = t->n_batch;
   if (segs[0].kv_bf16 != 0) return TBX_ERR_UNSUPPORTED;  // bf16 K/V tables: forward only
-  rc = set_dropout(b.f, p_drop, drop_seed, drop_call, time_batch, time0);
+  rc = set_drop(b.f, *t);
   if (rc != TBX_OK) return rc;
-  for (int i = 0; i < n_seg; ++i) {
-    if (!dkv[i]) return TBX_ERR_ARG;
-    b.dkv[i] = dkv[i];
+  b.dout = t->dout;
+  b.dqbuf = t->dqbuf;
+  b.dbias_k = t->dbias_k;
+  b.coef = t->coef;
+  hipStream_t hs = (hipStream_t)stream;
+  if (t->coef == nullptr) {  // dK / dV by atomicAdd
+    for (int i = 0; i < n_seg; ++i) {
+      if (!t->dkv[i]) return TBX_ERR_ARG;
+      b.dkv[i] = t->dkv[i];
+    }
+    if (n_seg == 1) b.dkv[1] = b.dkv[0];
+    if (b.dbias_k != nullptr) hipLaunchKernelGGL(knarpe_attn_bwd_kernel<true>, dim3((b.f.n_rows + 3) / 4), dim3(256), 0, hs, b);
+    else hipLaunchKernelGGL(knarpe_attn_bwd_kernel<false>, dim3((b.f.n_rows + 3) / 4), dim3(256), 0, hs, b);
+    return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
   }
-  if (n_seg == 1) b.dkv[1] = b.dkv[0];
-  b.dout = dout;
-  b.dqbuf = dqbuf;
-  b.dbias_k = dbias_k;
-  b.coef = nullptr;
-  if (dbias_k != nullptr) hipLaunchKernelGGL(knarpe_attn_bwd_kernel<true>, dim3((b.f.n_rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, b);
-  else hipLaunchKernelGGL(knarpe_attn_bwd_kernel<false>, dim3((b.f.n_rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, b);
-  return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
-}
-
-extern "C" int tbx_knarpe_attn_bwd_gather_tb(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias,
-                                             int n_batch, int n_src, const tbx_attn_seg_t* segs, int n_seg, const float* dout,
-                                             int ldo, float* dqbuf, float* const* dkv, float* dbias_k, const float* freqs_xy,
-                                             const float* freqs_yaw, float p_drop, const uint64_t* drop_seed, uint32_t drop_call,
-                                             int time_batch, int time0, const int32_t* const* inv_ptr,
-                                             const int32_t* const* inv_list, float* coef, void* stream) {
-  if (!dout || !dqbuf || !dkv || !inv_ptr || !inv_list || !coef) return TBX_ERR_ARG;  // (dbias_k may be NULL: not computed)
-  if ((((uintptr_t)dout) & 15) || (((uintptr_t)dqbuf) & 15)) return TBX_ERR_ALIGN;
-  AttnBwdArgs b;
-  int rc = fill_args(b.f, qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, ldo, freqs_xy, freqs_yaw);
-  if (rc != TBX_OK) return rc;
-  if (segs[0].kv_bf16 != 0) return TBX_ERR_UNSUPPORTED;  // bf16 K/V tables: forward only
-  rc = set_dropout(b.f, p_drop, drop_seed, drop_call, time_batch, time0);
-  if (rc != TBX_OK) return rc;
+  // dK / dV through the inverse lists: the row kernel stores coefficients, the dkv kernel sums them per target token
   DkvArgs d;
-  d.qbuf = qbuf, d.dout = dout, d.coef = coef;
-  d.ldq = ldq, d.q_off = q_off, d.ldo = ldo;
+  d.qbuf = t->qbuf, d.dout = t->dout, d.coef = t->coef;
+  d.ldq = t->ldq, d.q_off = t->q_off, d.ldo = t->ldo;
   int t_off = 0, tok = 0;
   for (int i = 0; i < 2; ++i) {
     const int s = i < n_seg ? i : 0;
-    if (i < n_seg && (!dkv[i] || !inv_ptr[i] || !inv_list[i] || (((uintptr_t)dkv[i]) & 15) || n_batch % segs[i].batch_div))
+    if (i < n_seg && (!t->dkv[i] || !t->inv_ptr[i] || !t->inv_list[i] || (((uintptr_t)t->dkv[i]) & 15) || n_batch % segs[i].batch_div))
       return TBX_ERR_ARG;
-    b.dkv[i] = dkv[s];
-    d.dkv[i] = dkv[s], d.inv_ptr[i] = inv_ptr[s], d.inv_list[i] = inv_list[s];
+    b.dkv[i] = t->dkv[s];
+    d.dkv[i] = t->dkv[s], d.inv_ptr[i] = t->inv_ptr[s], d.inv_list[i] = t->inv_list[s];
     d.k[i] = segs[s].k, d.n_tgt[i] = segs[s].n_tgt, d.ld_kv[i] = segs[s].ld_kv, d.k_off[i] = segs[s].k_off, d.v_off[i] = segs[s].v_off;
-    d.list_cap[i] = n_src * segs[s].batch_div * segs[s].k;
+    d.list_cap[i] = t->n_src * segs[s].batch_div * segs[s].k;
     d.t_off[i] = i < n_seg ? t_off : 0;
     d.tok0[i] = i < n_seg ? tok : 0x7fffffff;
     if (i < n_seg) {
@@ -1057,51 +990,9 @@ extern "C" int tbx_knarpe_attn_bwd_gather_tb(const float* qbuf, int ldq, int q_o
   d.n_tok = tok;
   d.xcd = (attn_xcd_mask() >> 1) & 1;
   b.f.xcd = d.xcd;
-  b.dout = dout;
-  b.dqbuf = dqbuf;
-  b.dbias_k = dbias_k;
-  b.coef = coef;
-  hipStream_t hs = (hipStream_t)stream;
-  if (dbias_k != nullptr) hipLaunchKernelGGL(knarpe_attn_bwd_kernel<true>, dim3((b.f.n_rows + 3) / 4), dim3(256), 0, hs, b);
+  if (b.dbias_k != nullptr) hipLaunchKernelGGL(knarpe_attn_bwd_kernel<true>, dim3((b.f.n_rows + 3) / 4), dim3(256), 0, hs, b);
   else hipLaunchKernelGGL(knarpe_attn_bwd_kernel<false>, dim3((b.f.n_rows + 3) / 4), dim3(256), 0, hs, b);
   if (hipGetLastError() != hipSuccess) return TBX_ERR_LAUNCH;
   hipLaunchKernelGGL(knarpe_attn_dkv_kernel, dim3((d.n_tok + 3) / 4), dim3(256), 0, hs, d);
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
-}
-
-extern "C" int tbx_knarpe_attn_bwd(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias, int n_batch,
-                                   int n_src, const tbx_attn_seg_t* segs, int n_seg, const float* dout, int ldo, float* dqbuf,
-                                   float* const* dkv, float* dbias_k, const float* freqs_xy, const float* freqs_yaw,
-                                   void* stream) {
-  return tbx_knarpe_attn_bwd_dropout_tb(qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, dout, ldo, dqbuf, dkv,
-                                        dbias_k, freqs_xy, freqs_yaw, 0.f, nullptr, 0u, 1, 0, stream);
-}
-
-// The per-call forms (time_batch = 1, time0 = 0): the mask is keyed by (call, row, target slot, head) alone.
-extern "C" int tbx_knarpe_attn_fwd_dropout(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias,
-                                           int n_batch, int n_src, const tbx_attn_seg_t* segs, int n_seg, float* out, int ldo,
-                                           uint8_t* row_no_valid, const float* freqs_xy, const float* freqs_yaw, float p_drop,
-                                           const uint64_t* drop_seed, uint32_t drop_call, void* stream) {
-  return tbx_knarpe_attn_fwd_dropout_tb(qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, out, ldo, row_no_valid,
-                                        freqs_xy, freqs_yaw, p_drop, drop_seed, drop_call, 1, 0, stream);
-}
-
-extern "C" int tbx_knarpe_attn_bwd_dropout(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias,
-                                           int n_batch, int n_src, const tbx_attn_seg_t* segs, int n_seg, const float* dout,
-                                           int ldo, float* dqbuf, float* const* dkv, float* dbias_k, const float* freqs_xy,
-                                           const float* freqs_yaw, float p_drop, const uint64_t* drop_seed, uint32_t drop_call,
-                                           void* stream) {
-  return tbx_knarpe_attn_bwd_dropout_tb(qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, dout, ldo, dqbuf, dkv,
-                                        dbias_k, freqs_xy, freqs_yaw, p_drop, drop_seed, drop_call, 1, 0, stream);
-}
-
-extern "C" int tbx_knarpe_attn_bwd_gather(const float* qbuf, int ldq, int q_off, int qt_off, const float* rpe_k_bias,
-                                          int n_batch, int n_src, const tbx_attn_seg_t* segs, int n_seg, const float* dout,
-                                          int ldo, float* dqbuf, float* const* dkv, float* dbias_k, const float* freqs_xy,
-                                          const float* freqs_yaw, float p_drop, const uint64_t* drop_seed, uint32_t drop_call,
-                                          const int32_t* const* inv_ptr, const int32_t* const* inv_list, float* coef,
-                                          void* stream) {
-  return tbx_knarpe_attn_bwd_gather_tb(qbuf, ldq, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, n_seg, dout, ldo, dqbuf, dkv,
-                                       dbias_k, freqs_xy, freqs_yaw, p_drop, drop_seed, drop_call, 1, 0, inv_ptr, inv_list, coef,
-                                       stream);
 }

@@ -37,6 +37,7 @@
 
 #include "../../include/tbx_hip.h"
 #include "attn_core.h"
+#include "attn_host.h"
 #include "tbx_common.h"
 
 
@@ -63,7 +64,7 @@ struct MArgs {
   float scale2;  // log2(e) / sqrt(d_head)
   // dropout on the attention probabilities (training, attention_rpe.py:171-172): the fields and the key of attn.hip's AttnArgs /
   // attn_core.h's DropKey - (seed, call, scene row, closed-loop step, global target slot, head) - so that the backward kernels
-  // (tbx_knarpe_attn_bwd_*: they recompute the probabilities and regenerate the mask) drop exactly what this forward dropped
+  // (tbx_knarpe_attn_bwd: they recompute the probabilities and regenerate the mask) drop exactly what this forward dropped
   const uint64_t* drop_seed;
   uint32_t drop_call, drop_thresh;
   float drop_scale;
@@ -413,37 +414,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
 }  // namespace
 
-static int mfma_launch(const float* qbuf, int ldq, int q_off, int qt_off, int n_batch, int n_src, const tbx_attn_seg_t* segs, int n_seg,
-                       float* out, int ldo, uint8_t* row_no_valid, const float* freqs_xy, const float* freqs_yaw, float p_drop,
-                       const uint64_t* drop_seed, uint32_t drop_call, int time_batch, int time0, void* stream) {
-  if (!qbuf || !segs || !out || !row_no_valid || !freqs_xy || !freqs_yaw || n_batch <= 0 || n_src <= 0) return TBX_ERR_ARG;
-  if (n_seg < 1 || n_seg > 2 || ldo < D + NH * DR) return TBX_ERR_UNSUPPORTED;
-  if ((ldq % 4) || (q_off % 4) || (qt_off % 4) || (ldo % 4) || (((uintptr_t)qbuf) & 15) || (((uintptr_t)out) & 15)) return TBX_ERR_ALIGN;
+extern "C" int tbx_knarpe_attn_fwd_mfma(const tbx_attn_t* t, void* stream) {
+  if (!t || !t->out || !t->row_no_valid || !t->freqs_xy || !t->freqs_yaw) return TBX_ERR_ARG;
   MArgs a;
-  int ktot = 0;
-  for (int i = 0; i < n_seg; ++i) {
-    const tbx_attn_seg_t& s = segs[i];
-    if (!s.kv || !s.idx || !s.invalid || !s.rel_pose || s.k <= 0 || s.n_tgt <= 0 || s.batch_div <= 0) return TBX_ERR_ARG;
-    if (s.emb != nullptr) return TBX_ERR_UNSUPPORTED;  // relative-pose form only
-    if ((s.ld_kv % 8) || (s.k_off % 8) || (s.v_off % 8) || (((uintptr_t)s.kv) & 15)) return TBX_ERR_ALIGN;
-    if ((s.kv_bf16 != 0) != (segs[0].kv_bf16 != 0)) return TBX_ERR_UNSUPPORTED;
-    if ((int64_t)s.n_tgt * s.ld_kv * 4 >= (1ll << 32)) return TBX_ERR_UNSUPPORTED;  // (32-bit byte offsets inside a batch entry's table)
-    ktot += s.k;
-    a.seg[i] = s;
-  }
-  if (n_seg == 1) a.seg[1] = a.seg[0];
-  if (ktot > KMAX) return TBX_ERR_UNSUPPORTED;
-  a.qbuf = qbuf, a.fxy = freqs_xy, a.fyaw = freqs_yaw, a.out = out, a.row_no_valid = row_no_valid;
-  a.ldq = ldq, a.q_off = q_off, a.qt_off = qt_off, a.ldo = ldo, a.n_rows = n_batch * n_src, a.n_src = n_src, a.n_seg = n_seg;
-  a.scale2 = 1.4426950408889634f / sqrtf((float)DH);
-  a.drop_seed = drop_seed, a.drop_call = drop_call, a.drop_thresh = 0u, a.drop_scale = 1.f, a.drop_time_batch = time_batch, a.drop_time0 = time0;
-  if (p_drop < 0.f || p_drop >= 1.f || time_batch < 1 || time0 < 0) return TBX_ERR_ARG;
-  if (p_drop > 0.f) {  // (threshold and scale exactly as attn.hip's set_dropout: the backward regenerates the mask from them)
-    if (!drop_seed) return TBX_ERR_ARG;
-    const double th = (double)p_drop * 4294967296.0;
-    a.drop_thresh = th < 1.0 ? 1u : (uint32_t)th;
-    a.drop_scale = 1.0f / (1.0f - p_drop);
-  }
+  int rc = fill_common(a, *t, t->ldo, true);
+  if (rc != TBX_OK) return rc;
+  rc = set_dropout(a, *t);
+  if (rc != TBX_OK) return rc;
+  a.out = t->out, a.row_no_valid = t->row_no_valid;
+  const tbx_attn_seg_t* segs = t->seg;
+  const int n_seg = t->n_seg, n_batch = t->n_batch;
   const bool drop = a.drop_thresh != 0u;
   bool shared = false;
   for (int i = 0; i < n_seg; ++i) shared = shared || segs[i].batch_div > 1;
@@ -481,19 +461,4 @@ static int mfma_launch(const float* qbuf, int ldq, int q_off, int qt_off, int n_
   else TBX_MFMA_LAUNCH(false, false);
 #undef TBX_MFMA_LAUNCH
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
-}
-
-extern "C" int tbx_knarpe_attn_fwd_mfma(const float* qbuf, int ldq, int q_off, int qt_off, int n_batch, int n_src,
-                                        const tbx_attn_seg_t* segs, int n_seg, float* out, int ldo, uint8_t* row_no_valid,
-                                        const float* freqs_xy, const float* freqs_yaw, void* stream) {
-  return mfma_launch(qbuf, ldq, q_off, qt_off, n_batch, n_src, segs, n_seg, out, ldo, row_no_valid, freqs_xy, freqs_yaw, 0.f, nullptr, 0u, 1, 0,
-                     stream);
-}
-
-extern "C" int tbx_knarpe_attn_fwd_mfma_dropout_tb(const float* qbuf, int ldq, int q_off, int qt_off, int n_batch, int n_src,
-                                                   const tbx_attn_seg_t* segs, int n_seg, float* out, int ldo, uint8_t* row_no_valid,
-                                                   const float* freqs_xy, const float* freqs_yaw, float p_drop, const uint64_t* drop_seed,
-                                                   uint32_t drop_call, int time_batch, int time0, void* stream) {
-  return mfma_launch(qbuf, ldq, q_off, qt_off, n_batch, n_src, segs, n_seg, out, ldo, row_no_valid, freqs_xy, freqs_yaw, p_drop, drop_seed,
-                     drop_call, time_batch, time0, stream);
 }

@@ -1,10 +1,10 @@
 // tbx_knarpe_dec_mid: the attention half of a dec_cross_attn transformer layer (transformer_rpe.py:207-233) as ONE launch for
 // launches of a few hundred rows (the closed loop at one or a few scenes):
 //
-//   self attention over the K nearest tokens (K/V rows of the table the previous launch stored)         [tbx_knarpe_attn_fwd_folded]
+//   self attention over the K nearest tokens (K/V rows of the table the previous launch stored)         [tbx_knarpe_attn_fwd, fold]
 //   x += rows without a valid target ? 0 : out_proj(.)                                                 [chain: LINEAR, accumulate, row skip]
 //   h = LayerNorm_1(x);  q = W_q h + b_q;  qt_h = W_rpe_k,h^T q_h                                        [chain: LN, LINEAR, grouped LINEAR]
-//   cross attention over the K nearest map tokens ++ K nearest traffic lights, value fold applied       [tbx_knarpe_attn_fwd_folded]
+//   cross attention over the K nearest map tokens ++ K nearest traffic lights, value fold applied       [tbx_knarpe_attn_fwd, fold]
 //
 // i.e. what ran as attention kernel -> row chain -> attention kernel: three dependent launches of ~12 + 15 + 15 us whose
 // work is a few hundred kFLOP per row. One workgroup (4 wavefronts) per row; the two target sweeps are attn_core.h's (4 waves

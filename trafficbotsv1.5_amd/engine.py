@@ -43,7 +43,7 @@ class Schedule:
     # per decoder layer. False: separate ROWMASK / ADD stages (results differ by fp32 rounding order only).
     fused_residual: bool = True
     load2: bool = True  # token rows + attention output loaded by one stage
-    # inference: the attention kernel applies the value half of linear_rpe in its epilogue (tbx_knarpe_attn_fwd_folded): 128 floats
+    # inference: the attention kernel applies the value half of linear_rpe in its epilogue (tbx_attn_t.fold_image): 128 floats
     # per row leave it instead of 640 and the grouped fold stage of the following chain disappears.
     attn_fold: bool = True
     # the wave-per-row form of the kernel (>= 1024 rows) has the folded epilogue too. Measured at the WOSAC shape (4096 rows x 104

@@ -15,7 +15,7 @@ from . import abi, hip_base
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
 from .abi import HEADER_PATH, LIB_PATH, load  # noqa: F401
 from .hip_base import *  # noqa: F401,F403  (Seg, stream_ptr, packed_weight / stacked_linear / padded_weight)
-from .hip_base import _check, _cptr, _drop_args, _ptr  # noqa: F401
+from .hip_base import _attn_args, _check, _cptr, _ptr  # noqa: F401
 from .hip_chain import *  # noqa: F401,F403  (Chain, group_tile_rows)
 from .hip_rules import *  # noqa: F401,F403  (rule_tables, rule_check, rule_accumulate, filter_futures, womd_modes, pose_to_global)
 from .hip_train import *  # noqa: F401,F403  (the training entry points)
@@ -125,43 +125,23 @@ def pose_embed(pose3, freqs_xy, freqs_yaw, pe_dim: int, out=None, col_off: int =
 
 def knarpe_attn(qbuf, q_off: int, qt_off: int, rpe_k_bias, n_batch: int, n_src: int, segs: Sequence[Seg], out, row_no_valid,
                 freqs_xy=None, freqs_yaw=None, drop=None, fold=None):
-    """drop = None, or (p, seed int64[1] device tensor, call id[, time_batch, time0]): attention-probability dropout
-    (training; the last two for time-batched calls, include/tbx_hip.h).
-    fold = the tbx_pack_weight_gemv image of linear_rpe's value half: tbx_knarpe_attn_fwd_folded, `out` is then [rows, >= 128]."""
-    arr = (AttnSeg * len(segs))(*[s.c() for s in segs])
-    if fold is not None:
-        assert drop is None
-        rc = load().tbx_knarpe_attn_fwd_folded(_ptr(qbuf, torch.float32), qbuf.stride(0), q_off, qt_off, _ptr(rpe_k_bias, torch.float32),
-                                               n_batch, n_src, arr, len(segs), _ptr(out, torch.float32), out.stride(0),
-                                               _ptr(row_no_valid, torch.uint8), _cptr(freqs_xy), _cptr(freqs_yaw),
-                                               _ptr(fold, torch.float32), stream_ptr())
-        _check(rc, "tbx_knarpe_attn_fwd_folded")
-        return
-    p, seed, call, tb, t0 = _drop_args(drop)
-    rc = load().tbx_knarpe_attn_fwd_dropout_tb(_ptr(qbuf, torch.float32), qbuf.stride(0), q_off, qt_off, _ptr(rpe_k_bias, torch.float32),
-                                            n_batch, n_src, arr, len(segs), _ptr(out, torch.float32), out.stride(0),
-                                            _ptr(row_no_valid, torch.uint8), _cptr(freqs_xy), _cptr(freqs_yaw), float(p),
-                                            _ptr(seed, torch.int64), int(call), tb, t0, stream_ptr())
-    _check(rc, "tbx_knarpe_attn_fwd")
+    """tbx_knarpe_attn_fwd. drop = None, or (p, seed int64[1] device tensor, call id[, time_batch, time0]): attention-probability
+    dropout (training; the last two for time-batched calls, include/tbx_hip.h).
+    fold = the tbx_pack_weight_gemv image of linear_rpe's value half (tbx_attn_t.fold_image): `out` is then [rows, >= 128]."""
+    assert fold is None or drop is None
+    a = _attn_args(qbuf, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, (freqs_xy, freqs_yaw), drop)
+    a.out, a.ldo, a.row_no_valid, a.fold_image = _ptr(out, torch.float32), out.stride(0), _ptr(row_no_valid, torch.uint8), _ptr(fold, torch.float32)
+    _check(load().tbx_knarpe_attn_fwd(C.byref(a), stream_ptr()), "tbx_knarpe_attn_fwd")
 
 
 def knarpe_attn_mfma(qbuf, q_off: int, qt_off: int, n_batch: int, n_src: int, segs: Sequence[Seg], out, row_no_valid, freqs_xy, freqs_yaw,
                      drop=None):
     """tbx_knarpe_attn_fwd_mfma: the wave-per-row forward on the bf16 matrix cores (bf16 operands, fp32 accumulation / softmax).
     Same `out` [rows, >= 640] / row_no_valid as knarpe_attn; segments in the relative-pose form. drop: as knarpe_attn's (training:
-    tbx_knarpe_attn_fwd_mfma_dropout_tb, the same mask as the VALU kernels draw for that key)."""
-    arr = (AttnSeg * len(segs))(*[s.c() for s in segs])
-    if drop is not None:
-        p, seed, call, tb, t0 = _drop_args(drop)
-        rc = load().tbx_knarpe_attn_fwd_mfma_dropout_tb(_ptr(qbuf, torch.float32), qbuf.stride(0), q_off, qt_off, n_batch, n_src, arr, len(segs),
-                                                        _ptr(out, torch.float32), out.stride(0), _ptr(row_no_valid, torch.uint8), _cptr(freqs_xy),
-                                                        _cptr(freqs_yaw), float(p), _ptr(seed, torch.int64), int(call), tb, t0, stream_ptr())
-        _check(rc, "tbx_knarpe_attn_fwd_mfma_dropout_tb")
-        return
-    rc = load().tbx_knarpe_attn_fwd_mfma(_ptr(qbuf, torch.float32), qbuf.stride(0), q_off, qt_off, n_batch, n_src, arr, len(segs),
-                                         _ptr(out, torch.float32), out.stride(0), _ptr(row_no_valid, torch.uint8), _cptr(freqs_xy),
-                                         _cptr(freqs_yaw), stream_ptr())
-    _check(rc, "tbx_knarpe_attn_fwd_mfma")
+    the same mask as the VALU kernels draw for that key)."""
+    a = _attn_args(qbuf, q_off, qt_off, None, n_batch, n_src, segs, (freqs_xy, freqs_yaw), drop)
+    a.out, a.ldo, a.row_no_valid = _ptr(out, torch.float32), out.stride(0), _ptr(row_no_valid, torch.uint8)
+    _check(load().tbx_knarpe_attn_fwd_mfma(C.byref(a), stream_ptr()), "tbx_knarpe_attn_fwd_mfma")
 
 
 # ---- deferred launches (round 6: RolloutEngine's one-queue step). While a list is installed, tbx_front / tbx_knarpe_dec_layer calls

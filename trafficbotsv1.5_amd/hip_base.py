@@ -59,12 +59,18 @@ class Seg:
                        self.n_tgt, self.batch_div, self.k, int(self.kv.dtype == torch.bfloat16))
 
 
-def _drop_args(drop):
-    if drop is None:
-        return 0.0, None, 0, 1, 0
-    p, seed, call = drop[:3]
-    tb, t0 = (drop[3], drop[4]) if len(drop) > 3 else (1, 0)
-    return p, seed, call, int(tb), int(t0)
+def _attn_args(qbuf, q_off: int, qt_off: int, rpe_k_bias, n_batch: int, n_src: int, segs: Sequence[Seg], freqs, drop) -> Attn:
+    """The part of tbx_attn_t every attention entry point reads: query side, segments, freqs = (freqs_xy, freqs_yaw) and
+    drop = None, or (p, seed int64[1] device tensor, call id[, time_batch, time0]). The caller adds its outputs / gradients."""
+    a = Attn(qbuf=_ptr(qbuf, torch.float32), rpe_k_bias=_ptr(rpe_k_bias, torch.float32), freqs_xy=_cptr(freqs[0]), freqs_yaw=_cptr(freqs[1]),
+             ldq=qbuf.stride(0), q_off=q_off, qt_off=qt_off, n_batch=n_batch, n_src=n_src, n_seg=len(segs), time_batch=1)
+    for i, s in enumerate(segs[:2]):  # (a third segment is the library's to refuse: n_seg says so)
+        a.seg[i] = s.c()
+    if drop is not None:
+        a.p_drop, a.drop_seed, a.drop_call = float(drop[0]), _ptr(drop[1], torch.int64), int(drop[2])
+        if len(drop) > 3:
+            a.time_batch, a.time0 = int(drop[3]), int(drop[4])
+    return a
 
 
 def weights_stamp(tensors) -> tuple:

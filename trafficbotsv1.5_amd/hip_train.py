@@ -9,7 +9,7 @@ import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
 from .abi import load  # noqa: F401
-from .hip_base import Seg, _check, _cptr, _derived, _drop_args, _name, _ptr, packed_weight, stream_ptr
+from .hip_base import Seg, _attn_args, _check, _cptr, _derived, _name, _ptr, packed_weight, stream_ptr
 
 
 def keyed_dropout(x: torch.Tensor, p: float, seed: torch.Tensor, site: int, rows_per_scene: int, time_batch: int = 1,
@@ -277,16 +277,21 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, mean: 
     return dx, dg, db
 
 
+def _attn_bwd(qbuf, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, dout, dqbuf, dkv, dbias_k, freqs_xy, freqs_yaw, drop, inv=None, coef=None):
+    """tbx_knarpe_attn_bwd: coef / inv = None for the atomics form, the scratch and the inverse lists for the form without."""
+    a = _attn_args(qbuf, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, (freqs_xy, freqs_yaw), drop)
+    a.dout, a.ldo, a.dqbuf, a.dbias_k, a.coef = _ptr(dout, torch.float32), dout.stride(0), _ptr(dqbuf, torch.float32), _ptr(dbias_k, torch.float32), _ptr(coef)
+    for i in range(min(len(segs), 2)):
+        a.dkv[i] = _ptr(dkv[i], torch.float32)
+        if inv is not None:
+            a.inv_ptr[i], a.inv_list[i] = _cptr(inv[i][0], torch.int32), _cptr(inv[i][1], torch.int32)
+    _check(load().tbx_knarpe_attn_bwd(C.byref(a), stream_ptr()), "tbx_knarpe_attn_bwd")
+
+
 def knarpe_attn_bwd(qbuf, q_off: int, qt_off: int, rpe_k_bias, n_batch: int, n_src: int, segs: Sequence[Seg], dout, dqbuf,
                     dkv: Sequence[torch.Tensor], dbias_k, freqs_xy=None, freqs_yaw=None, drop=None):
-    arr = (AttnSeg * len(segs))(*[s.c() for s in segs])
-    dk = (C.c_void_p * len(segs))(*[_ptr(t, torch.float32) for t in dkv])
-    p, seed, call, tb, t0 = _drop_args(drop)
-    rc = load().tbx_knarpe_attn_bwd_dropout_tb(_ptr(qbuf, torch.float32), qbuf.stride(0), q_off, qt_off, _ptr(rpe_k_bias, torch.float32),
-                                            n_batch, n_src, arr, len(segs), _ptr(dout, torch.float32), dout.stride(0),
-                                            _ptr(dqbuf, torch.float32), dk, _ptr(dbias_k, torch.float32), _cptr(freqs_xy),
-                                            _cptr(freqs_yaw), float(p), _ptr(seed, torch.int64), int(call), tb, t0, stream_ptr())
-    _check(rc, "tbx_knarpe_attn_bwd")
+    """dK / dV are accumulated into dkv with atomics (zero it first)."""
+    _attn_bwd(qbuf, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, dout, dqbuf, dkv, dbias_k, freqs_xy, freqs_yaw, drop)
 
 
 def knn_inverse(idx, invalid, n_tgt: int, tgt_batch_div: int = 1):
@@ -304,18 +309,8 @@ def knn_inverse(idx, invalid, n_tgt: int, tgt_batch_div: int = 1):
 def knarpe_attn_bwd_gather(qbuf, q_off: int, qt_off: int, rpe_k_bias, n_batch: int, n_src: int, segs: Sequence[Seg], dout, dqbuf,
                            dkv: Sequence[torch.Tensor], dbias_rows, inv: Sequence, freqs_xy=None, freqs_yaw=None, drop=None):
     """Backward through inverse K-nearest lists (inv[i] = knn_inverse(...) of segment i): no dK / dV atomics."""
-    arr = (AttnSeg * len(segs))(*[s.c() for s in segs])
-    dk = (C.c_void_p * len(segs))(*[_ptr(t, torch.float32) for t in dkv])
-    ip = (C.c_void_p * len(segs))(*[_cptr(p, torch.int32) for p, _ in inv])
-    il = (C.c_void_p * len(segs))(*[_cptr(l, torch.int32) for _, l in inv])
     coef = torch.empty(n_batch * n_src, sum(s.k for s in segs), 8, dtype=torch.float32, device=qbuf.device)
-    p, seed, call, tb, t0 = _drop_args(drop)
-    rc = load().tbx_knarpe_attn_bwd_gather_tb(_ptr(qbuf, torch.float32), qbuf.stride(0), q_off, qt_off, _ptr(rpe_k_bias, torch.float32),
-                                           n_batch, n_src, arr, len(segs), _ptr(dout, torch.float32), dout.stride(0),
-                                           _ptr(dqbuf, torch.float32), dk, _ptr(dbias_rows, torch.float32), _cptr(freqs_xy),
-                                           _cptr(freqs_yaw), float(p), _ptr(seed, torch.int64), int(call), tb, t0, ip, il, _ptr(coef),
-                                           stream_ptr())
-    _check(rc, "tbx_knarpe_attn_bwd_gather")
+    _attn_bwd(qbuf, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, dout, dqbuf, dkv, dbias_rows, freqs_xy, freqs_yaw, drop, inv, coef)
 
 
 def dropout_keep_mask(seed: int, call: int, n_rows: int, k_tot: int, p: float, n_head: int = 4, step: int = 0) -> torch.Tensor:

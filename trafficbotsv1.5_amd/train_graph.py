@@ -1,12 +1,13 @@
 """Differentiable (training) schedule of the hot path on the GPU.
 
-Forward AND backward of the KNARPE attention are hand-written HIP kernels (tbx_knarpe_attn_fwd / _bwd) behind
-`KnarpeAttnFn`; K-nearest selection, pose embeddings and feature preparation are the same HIP kernels as in inference
-(no gradient flows through them: the reference computes them under no_grad, utils/rpe.py:7,40,61). The dense
-projections are plain library GEMMs (`F.linear` -> hipBLASLt) and the LayerNorm / ReLU / masking / max-pool glue is
-elementwise torch on the device, so autograd provides their backward. Fusing those into chain-backward kernels is the
-next step; the formulation (K/V projected before the gather, linear_rpe folded) is identical to the
-inference engine, so both are checked against the same oracle.
+Forward AND backward of the KNARPE attention are hand-written HIP kernels (tbx_knarpe_attn_fwd / _fwd_mfma / _bwd on one
+tbx_attn_t) behind `KnarpeAttnFn`; K-nearest selection, pose embeddings and feature preparation are the same HIP kernels as in
+inference (no gradient flows through them: the reference computes them under no_grad, utils/rpe.py:7,40,61). The dense
+projections over the time-batched rows, their input and weight gradients, LayerNorm and the dropout / residual / ReLU / max-pool
+glue are HIP kernels with hand-written backwards as well (tbx_tall_linear*, tbx_linear_wgrad*, tbx_layernorm_*, tbx_*_drop_*,
+tbx_pointnet_tail_*: the autograd Functions of train_ops.py); what falls outside their shapes is torch on the device. The
+formulation (K/V projected before the gather, linear_rpe folded) is identical to the inference engine, so both are checked
+against the same oracle.
 
 Everything takes the reference-named nn.Modules as parameter containers (same state dict as inference).
 This module assembles the encoders, the policy step, the two rollout forms, the loss and `training_step`; the autograd Functions

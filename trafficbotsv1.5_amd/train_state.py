@@ -13,7 +13,7 @@ import torch
 # configs/trainer/default.yaml:16):
 #   "bf16"  ONE bf16 product per term, fp32 accumulation: F.linear forward / input gradient over >= WGRAD_MIN_ROWS rows
 #           (tbx_tall_linear_bf16), their weight gradients (tbx_linear_wgrad_bf16), the attention forward of the differentiated launches
-#           (>= 193 source rows; tbx_knarpe_attn_fwd_mfma_dropout_tb: bf16 q, qt, K, V, e and softmax weights on the matrix cores). LayerNorm,
+#           (>= 193 source rows; tbx_knarpe_attn_fwd_mfma with dropout: bf16 q, qt, K, V, e and softmax weights on the matrix cores). LayerNorm,
 #           softmax, the attention backward (it recomputes the probabilities in fp32 and regenerates the forward's dropout mask), the
 #           elementwise glue, the state machine, the losses and the optimizer stay fp32 - as under autocast. The default.
 #   "fp32"  the fp32-class path of rounds 2-4 (split-bf16 products / exact-fp32 MFMA, VALU attention): the tight-tolerance parity path
