@@ -507,7 +507,12 @@ int tbx_knn_inverse(const int32_t* idx, const uint8_t* invalid, int n_batch, int
  * 93-131 in training): y[row, c] = x[row, c] * keep / (1 - p), keep = hash(seed, site, step, scene row, c) >= p * 2^32.
  * x, y [rows, cols] contiguous (y may alias x); rows_per_scene rows per batch entry; batch entry b = row / rows_per_scene is
  * step time0 + b % time_batch of scene b / time_batch (tbx_attn_t's time-batched calls), scene row = (b / time_batch) * rows_per_scene + row %
- * rows_per_scene. Its own backward (the gradient takes the same mask). `site` distinguishes the dropout sites of a step. */
+ * rows_per_scene. Its own backward (the gradient takes the same mask). `site` distinguishes the dropout sites of a step.
+ * The threshold and the scale come from the FLOAT p_drop (csrc/drop_key.h, the one definition of the mask and of this rule):
+ *   th = (double)p_drop * 4294967296.0;  threshold = th < 1 ? 1 : (uint32_t)th;  scale = 1.0f / (1.0f - p_drop)   (float arithmetic)
+ * e.g. p_drop = 0.1f -> 429496736 (not (uint32_t)(0.1 * 2^32) = 429496729). The drop_thresh / drop_scale fields of tbx_layer_tile_t,
+ * tbx_heads_tile_t and tbx_window_tile_t and a TBX_OP_DROPOUT stage's reserved / f0 must hold exactly these values for the p_drop of the
+ * other launches of the same training step: only then are the masks equal. */
 int tbx_keyed_dropout(const float* x, float* y, int64_t rows, int cols, int rows_per_scene, float p_drop,
                       const uint64_t* drop_seed /* device */, uint32_t site, int time_batch, int time0, void* stream);
 
@@ -674,8 +679,8 @@ enum {
   TBX_OP_STORE = 9,     /* p0[g * ld + dst_col + c] = src[:, src_col + c] for valid rows */
   TBX_OP_CLAMP = 10,    /* dst[:, dst_col:+n] = clamp(dst, f0, f1) */
   TBX_OP_DROPOUT = 11   /* dst[g, dst_col + c] *= keep ? f0 : 0 with tbx_keyed_dropout's mask for (seed = *(u64*)p0, site = div, step = k,
-                           scene row = global row g, column c of n): keep = hash >= threshold = (uint32_t)reserved (p * 2^32),
-                           f0 = 1 / (1 - p). The stepping (no-grad) pass of training runs its layers as chains with these stages. */
+                           scene row = global row g, column c of n): keep = hash >= threshold = (uint32_t)reserved,
+                           f0 = scale (both by tbx_keyed_dropout's rule for the float p). The stepping (no-grad) pass of training runs its layers as chains with these stages. */
 };
 enum { TBX_ACT_NONE = 0, TBX_ACT_RELU = 1 };
 enum {

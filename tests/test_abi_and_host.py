@@ -116,6 +116,59 @@ def test_ctypes_mirrors_have_the_layout_gcc_gives_the_header(hip, tmp_path):
         assert getattr(t, f).offset == off, (c, f, getattr(t, f).offset, off)
 
 
+def test_python_dropout_rule_equals_drop_key_header(hip, tmp_path):
+    """csrc/drop_key.h - the one definition of the keyed-dropout mask - compiled by a plain g++ (no HIP), against its Python restatement
+    in hip_base: (thresh, scale) of p, the stream key of (seed, site, step), the hash, the row key, and hip_train.dropout_keep_mask."""
+    import subprocess
+    from pathlib import Path
+    B, T = import_module("trafficbots_amd.hip_base"), import_module("trafficbots_amd.hip_train")
+    root = Path(__file__).resolve().parent.parent
+    ps = [0.05, 0.1, 0.15, 0.2, 0.3, 0.5, 0.999, 1e-11]
+    keys = [(0, 0, 0), (1, 2, 3), (0x0123456789ABCDEF, 7, 90), (2**64 - 1, 0xFFFFFFFF, 0xFFFFFFFF), (-5 % 2**64, 41, 10), (977, 1000003, 79)]
+    counters = [0, 1, 2, 3, 127, 128, 511, 512, 65535, 65536, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFE, 0xFFFFFFFF, 123456789, 3141592653]
+    rows = [(0, 1, 1, 0), (5, 1, 1, 3), (17, 4, 1, 0), (17, 4, 3, 2), (1000, 7, 5, 11), (2_000_000_123, 640, 80, 10)]  # row, rows_per_scene, time_batch, time0
+    seed, call, step, p_mask, shape = 0x5DEECE66D, 3, 12, 0.1, (5, 4, 24)  # dropout_keep_mask's (n_rows, n_head, k_tot)
+    arr = lambda name, ty, vals: f"const {ty} {name}[] = {{" + ", ".join(vals) + "};\n"
+    src = tmp_path / "dk.cpp"
+    src.write_text('#include "drop_key.h"\n#include <stdio.h>\nusing namespace tbx_drop;\n' +
+                   arr("ps", "float", [repr(p) + "f" for p in ps]) + arr("cs", "uint32_t", [f"{c}u" for c in counters]) +
+                   arr("ks", "uint64_t", [f"{v}ull" for k in keys for v in k]) + arr("rs", "int64_t", [f"{v}ll" for r in rows for v in r]) +
+                   "int main() {\n"
+                   "  for (float p : ps) { const Rate r = drop_rate(p); printf(\"%u %.9g\\n\", r.thresh, r.scale); }\n"
+                   f"  for (int i = 0; i < {len(keys)}; ++i) {{\n"
+                   "    const StreamKey k = stream_key(ks[3 * i], (uint32_t)ks[3 * i + 1], (uint32_t)ks[3 * i + 2]);\n"
+                   "    printf(\"%u %u\\n\", k.lo, k.hi);\n"
+                   "    for (uint32_t c : cs) printf(\"%u\\n\", drop_mix(c, k.lo, k.hi));\n  }\n"
+                   f"  for (int i = 0; i < {len(rows)}; ++i) {{\n"
+                   "    const int64_t* r = rs + 4 * i;\n"
+                   "    const RowKey a = row_key<int64_t>(r[0], (int)r[1], (int)r[2], (int)r[3]), b = row_key<uint32_t>((uint32_t)r[0], (int)r[1], (int)r[2], (int)r[3]);\n"
+                   "    const RowKey c = row_key<int>((int)r[0], (int)(r[0] / r[1]), (int)r[1], (int)r[2], (int)r[3]);\n"
+                   "    printf(\"%u %u %u %u %u %u\\n\", a.step, a.scene_row, b.step, b.scene_row, c.step, c.scene_row);\n  }\n"
+                   f"  const StreamKey k = stream_key({seed}ull, {call}u, {step}u);\n"
+                   f"  for (uint32_t row = 0; row < {shape[0]}; ++row) for (uint32_t h = 0; h < {shape[1]}; ++h) for (uint32_t t = 0; t < {shape[2]}; ++t)\n"
+                   f"    printf(\"%d\\n\", (int)(drop_mix((row * 128u + t) * 4u + h, k.lo, k.hi) >= drop_rate({p_mask!r}f).thresh));\n"
+                   "  return 0;\n}\n")
+    exe = tmp_path / "dk"
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", str(root / "trafficbotsv1.5_amd" / "csrc"), str(src), "-o", str(exe)], check=True)
+    out = iter(subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n"))
+    for p in ps:
+        th, sc = next(out).split()
+        got = B.drop_rate(p)
+        assert (int(th), np.float32(float(sc))) == (got[0], np.float32(got[1])), (p, th, sc, got)
+    assert B.drop_rate(0.1)[0] == 429496736 and B.drop_rate(1e-11)[0] == 1 and B.drop_rate(0.0) == (0, 1.0)
+    for k in keys:
+        lo, hi = (int(v) for v in next(out).split())
+        assert B.drop_stream_key(*k) == (lo, hi), k
+        want = [int(next(out)) for _ in counters]
+        assert B.drop_mix(np.array(counters, dtype=np.uint32), lo, hi).tolist() == want, k
+    for row, rps, tb_, t0 in rows:  # batch entry b = row // rps is step t0 + b % time_batch of scene b // time_batch
+        b = row // rps
+        assert [int(v) for v in next(out).split()] == [t0 + b % tb_, (b // tb_) * rps + row % rps] * 3, (row, rps, tb_, t0)
+    want = torch.tensor([int(next(out)) for _ in range(shape[0] * shape[1] * shape[2])], dtype=torch.bool).view(shape)
+    got = T.dropout_keep_mask(seed, call, shape[0], shape[2], p_mask, n_head=shape[1], step=step)
+    assert got.dtype == torch.bool and torch.equal(got, want) and 0 < int((~want).sum()) < want.numel() // 2
+
+
 def test_new_entry_points_validate_arguments_without_a_gpu(hip):
     lib = hip.load()
     assert lib.tbx_keyed_dropout(None, None, 4, 4, 2, 0.1, None, 0, 1, 0, None) == -1

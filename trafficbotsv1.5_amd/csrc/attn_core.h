@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/tbx_hip.h"
+#include "drop_key.h"
 #include "tbx_common.h"
 
 namespace tbx_attn {
@@ -90,29 +91,18 @@ __device__ __forceinline__ void sincos_rev(float arg, float* sn, float* cs) {
   *cs = __builtin_amdgcn_cosf(f);
 }
 
-// Dropout mask bit of (row, global target slot t < 128, head): lowbias32 finaliser over a counter keyed by the seed.
+// Dropout mask bit of (row, global target slot t < 128, head): drop_key.h's mask over the counter (scene row * 128 + t) * 4 + head.
 struct DropKey {
   uint32_t lo, hi, krow;
-  // row: the wave's source row (uniform); b = row / n_src
+  // row: the wave's source row (uniform); b = row / n_src (a scene's rows are its n_src sources)
   template <class A>
   __device__ __forceinline__ void init(const A& a, int row, int b) {
-    const uint64_t sd = *a.drop_seed;
-    const int sc = b / a.drop_time_batch;
-    const uint32_t ts = (uint32_t)(a.drop_time0 + (b - sc * a.drop_time_batch));
-    krow = (uint32_t)(sc * a.n_src + (row - b * a.n_src));
-    lo = (uint32_t)sd ^ (a.drop_call * 0x85EBCA6Bu) ^ (ts * 0x27D4EB2Fu);
-    hi = (uint32_t)(sd >> 32) + a.drop_call * 0xC2B2AE35u + ts * 0x165667B1u;
+    const tbx_drop::RowKey rk = tbx_drop::row_key<int>(row, b, a.n_src, a.drop_time_batch, a.drop_time0);
+    const tbx_drop::StreamKey sk = tbx_drop::stream_key(*a.drop_seed, a.drop_call, rk.step);
+    krow = rk.scene_row, lo = sk.lo, hi = sk.hi;
   }
   __device__ __forceinline__ bool keep(uint32_t t, uint32_t h, uint32_t thresh) const {
-    uint32_t x = ((krow * 128u + t) * 4u + h) ^ lo;
-    x *= 0x9E3779B1u;
-    x ^= hi;
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x >= thresh;
+    return tbx_drop::drop_mix((krow * 128u + t) * 4u + h, lo, hi) >= thresh;
   }
 };
 

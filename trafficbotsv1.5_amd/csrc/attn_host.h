@@ -50,23 +50,22 @@ inline int fill_common(A& a, const tbx_attn_t& t, int ldo, bool mfma) {
   return TBX_OK;
 }
 
-// The dropout fields of A from t's: drop when hash < drop_thresh = p * 2^32, survivors scaled by 1 / (1 - p). drop_thresh != 0
-// exactly when p_drop > 0.
+// The dropout fields of A from t's (drop_key.h: drop_rate). drop_thresh != 0 exactly when p_drop > 0.
 template <class A>
 inline int set_dropout(A& a, const tbx_attn_t& t) {
   a.drop_seed = t.drop_seed;
   a.drop_call = t.drop_call;
-  a.drop_thresh = 0u;
-  a.drop_scale = 1.f;
   a.drop_time_batch = t.time_batch;
   a.drop_time0 = t.time0;
+  a.drop_thresh = 0u;
+  a.drop_scale = 1.f;
+  // (time_batch and time0 are held to their ranges without dropout too; the rows are n_batch whole scenes of n_src > 0 rows, which
+  // fill_common has checked by now, so of the key's arguments only the seed can still be wrong)
   if (t.p_drop < 0.f || t.p_drop >= 1.f || t.time_batch < 1 || t.time0 < 0) return TBX_ERR_ARG;
-  if (t.p_drop > 0.f) {
-    if (!t.drop_seed) return TBX_ERR_ARG;
-    const double th = (double)t.p_drop * 4294967296.0;
-    a.drop_thresh = th < 1.0 ? 1u : (uint32_t)th;
-    a.drop_scale = 1.0f / (1.0f - t.p_drop);
-  }
+  if (t.p_drop > 0.f && !tbx_drop::key_args_ok(t.drop_seed, (int64_t)t.n_batch * t.n_src, t.n_src, t.time_batch, t.time0)) return TBX_ERR_ARG;
+  const tbx_drop::Rate r = tbx_drop::drop_rate(t.p_drop);
+  a.drop_thresh = r.thresh;
+  a.drop_scale = r.scale;
   return TBX_OK;
 }
 

@@ -7,9 +7,12 @@
 #include <stdint.h>
 
 #include "../../include/tbx_hip.h"
+#include "drop_key.h"
 #include "tbx_common.h"
 
 namespace {
+
+using namespace tbx_drop;
 
 struct DropArgs {
   const float* x;
@@ -21,18 +24,6 @@ struct DropArgs {
   float scale;
 };
 
-__device__ __forceinline__ uint32_t mix(uint32_t x, uint32_t lo, uint32_t hi) {
-  x ^= lo;
-  x *= 0x9E3779B1u;
-  x ^= hi;
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
 // One thread per float4 (VEC = 4, cols % 4 == 0, 16-byte aligned) or per element (VEC = 1).
 template <int VEC>
 __global__ __launch_bounds__(256) void keyed_dropout_kernel(const DropArgs a) {
@@ -42,23 +33,19 @@ __global__ __launch_bounds__(256) void keyed_dropout_kernel(const DropArgs a) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int64_t row = e / cv;
     const int c = (int)(e - row * cv) * VEC;
-    const int64_t b = row / a.rows_per_scene;
-    const int64_t sc = b / a.time_batch;
-    const uint32_t ts = (uint32_t)(a.time0 + (int)(b - sc * a.time_batch));
-    const uint32_t krow = (uint32_t)(sc * a.rows_per_scene + (row - b * a.rows_per_scene));
-    const uint32_t lo = (uint32_t)sd ^ (a.site * 0x85EBCA6Bu) ^ (ts * 0x27D4EB2Fu);
-    const uint32_t hi = (uint32_t)(sd >> 32) + a.site * 0xC2B2AE35u + ts * 0x165667B1u;
-    const uint32_t base = krow * (uint32_t)a.cols + (uint32_t)c;
+    const RowKey rk = row_key<int64_t>(row, a.rows_per_scene, a.time_batch, a.time0);
+    const StreamKey sk = stream_key(sd, a.site, rk.step);
+    const uint32_t base = rk.scene_row * (uint32_t)a.cols + (uint32_t)c;
     if constexpr (VEC == 4) {
       const float4 v = *(const float4*)(a.x + row * a.cols + c);
       float4 o;
-      o.x = mix(base + 0u, lo, hi) >= a.thresh ? v.x * a.scale : 0.f;
-      o.y = mix(base + 1u, lo, hi) >= a.thresh ? v.y * a.scale : 0.f;
-      o.z = mix(base + 2u, lo, hi) >= a.thresh ? v.z * a.scale : 0.f;
-      o.w = mix(base + 3u, lo, hi) >= a.thresh ? v.w * a.scale : 0.f;
+      o.x = drop_mix(base + 0u, sk.lo, sk.hi) >= a.thresh ? v.x * a.scale : 0.f;
+      o.y = drop_mix(base + 1u, sk.lo, sk.hi) >= a.thresh ? v.y * a.scale : 0.f;
+      o.z = drop_mix(base + 2u, sk.lo, sk.hi) >= a.thresh ? v.z * a.scale : 0.f;
+      o.w = drop_mix(base + 3u, sk.lo, sk.hi) >= a.thresh ? v.w * a.scale : 0.f;
       *(float4*)(a.y + row * a.cols + c) = o;
     } else {
-      a.y[row * a.cols + c] = mix(base, lo, hi) >= a.thresh ? a.x[row * a.cols + c] * a.scale : 0.f;
+      a.y[row * a.cols + c] = drop_mix(base, sk.lo, sk.hi) >= a.thresh ? a.x[row * a.cols + c] * a.scale : 0.f;
     }
   }
 }
@@ -89,15 +76,11 @@ __device__ __forceinline__ Keep4 keep4(const GlueArgs& a, uint64_t sd, int64_t r
     r.k[0] = r.k[1] = r.k[2] = r.k[3] = true;
     return r;
   }
-  const int64_t b = row / a.rows_per_scene;
-  const int64_t sc = b / a.time_batch;
-  const uint32_t ts = (uint32_t)(a.time0 + (int)(b - sc * a.time_batch));
-  const uint32_t krow = (uint32_t)(sc * a.rows_per_scene + (row - b * a.rows_per_scene));
-  const uint32_t lo = (uint32_t)sd ^ (a.site * 0x85EBCA6Bu) ^ (ts * 0x27D4EB2Fu);
-  const uint32_t hi = (uint32_t)(sd >> 32) + a.site * 0xC2B2AE35u + ts * 0x165667B1u;
-  const uint32_t base = krow * (uint32_t)a.cols + (uint32_t)c;
+  const RowKey rk = row_key<int64_t>(row, a.rows_per_scene, a.time_batch, a.time0);
+  const StreamKey sk = stream_key(sd, a.site, rk.step);
+  const uint32_t base = rk.scene_row * (uint32_t)a.cols + (uint32_t)c;
 #pragma unroll
-  for (int q = 0; q < 4; ++q) r.k[q] = mix(base + (uint32_t)q, lo, hi) >= a.thresh;
+  for (int q = 0; q < 4; ++q) r.k[q] = drop_mix(base + (uint32_t)q, sk.lo, sk.hi) >= a.thresh;
   return r;
 }
 
@@ -154,11 +137,10 @@ int glue_launch(int mode, GlueArgs a, float p_drop, const uint64_t* drop_seed, u
   if (p_drop < 0.f || p_drop >= 1.f) return TBX_ERR_ARG;
   a.seed = drop_seed, a.site = site, a.thresh = 0u, a.scale = 1.0f;
   a.rows_per_scene = 1, a.time_batch = 1, a.time0 = 0;
-  if (p_drop > 0.f) {
-    if (!drop_seed || rows_per_scene <= 0 || time_batch < 1 || time0 < 0 || a.rows % rows_per_scene) return TBX_ERR_ARG;
-    const double th = (double)p_drop * 4294967296.0;
-    a.thresh = th < 1.0 ? 1u : (uint32_t)th;
-    a.scale = 1.0f / (1.0f - p_drop);
+  if (p_drop > 0.f) {  // (p == 0 is "no dropout" here: the key's arguments are then not looked at)
+    if (!key_args_ok(drop_seed, a.rows, rows_per_scene, time_batch, time0)) return TBX_ERR_ARG;
+    const Rate r = drop_rate(p_drop);
+    a.thresh = r.thresh, a.scale = r.scale;
     a.rows_per_scene = rows_per_scene, a.time_batch = time_batch, a.time0 = time0;
   }
   const int64_t total = a.rows * (a.cols / 4);
@@ -211,7 +193,7 @@ extern "C" int tbx_relu_drop_bwd(const float* dh, const float* h, int64_t rows, 
   if (rows == 0) return TBX_OK;
   GlueArgs a{dh, h, nullptr, nullptr, dz, nullptr, rows, cols};
   // the mask is read off h: only the scale of the dropout is needed here
-  a.seed = nullptr, a.site = 0, a.thresh = 0u, a.scale = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
+  a.seed = nullptr, a.site = 0, a.thresh = 0u, a.scale = drop_rate(p_drop).scale;
   a.rows_per_scene = 1, a.time_batch = 1, a.time0 = 0;
   const int64_t total = rows * (cols / 4);
   const int64_t want = (total + 255) / 256;
@@ -258,16 +240,14 @@ extern "C" int tbx_pair_bias_relu(float* h, const float* pa, const float* pm, in
 
 extern "C" int tbx_keyed_dropout(const float* x, float* y, int64_t rows, int cols, int rows_per_scene, float p_drop,
                                  const uint64_t* drop_seed, uint32_t site, int time_batch, int time0, void* stream) {
-  if (!x || !y || !drop_seed || rows < 0 || cols <= 0 || rows_per_scene <= 0 || time_batch < 1 || time0 < 0) return TBX_ERR_ARG;
-  if (p_drop <= 0.f || p_drop >= 1.f) return TBX_ERR_ARG;
-  if (rows % rows_per_scene) return TBX_ERR_ARG;
+  if (!x || !y || rows < 0 || cols <= 0 || !key_args_ok(drop_seed, rows, rows_per_scene, time_batch, time0)) return TBX_ERR_ARG;
+  if (p_drop <= 0.f || p_drop >= 1.f) return TBX_ERR_ARG;  // (unlike the glue ops, p == 0 is an error: this call IS the dropout)
   if (rows == 0) return TBX_OK;
   DropArgs a;
   a.x = x, a.y = y, a.rows = rows, a.cols = cols, a.rows_per_scene = rows_per_scene, a.time_batch = time_batch, a.time0 = time0;
   a.seed = drop_seed, a.site = site;
-  const double th = (double)p_drop * 4294967296.0;
-  a.thresh = th < 1.0 ? 1u : (uint32_t)th;
-  a.scale = 1.0f / (1.0f - p_drop);
+  const Rate r = drop_rate(p_drop);
+  a.thresh = r.thresh, a.scale = r.scale;
   const bool vec = (cols % 4 == 0) && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
   const int64_t total = rows * (vec ? cols / 4 : cols);
   const int64_t want = (total + 255) / 256;

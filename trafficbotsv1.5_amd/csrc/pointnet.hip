@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/tbx_hip.h"
+#include "drop_key.h"
 #include "tbx_common.h"
 
 namespace {
@@ -16,19 +17,6 @@ namespace {
 constexpr int PN_C = 64;      // channels of a layer's Linear (one per lane); the layer's output is 2 * PN_C wide
 constexpr int PN_MAXW = 32;   // rows per group kept in registers: the kernels come in two sizes, <MAXW = 16> (the windows of 11) and <32> (the map's polylines of 20 nodes, the posterior's windows of 19)
 constexpr int PN_WAVES = 4;
-
-// tbx_keyed_dropout's hash (csrc/dropout.hip)
-__device__ __forceinline__ uint32_t mix(uint32_t x, uint32_t lo, uint32_t hi) {
-  x ^= lo;
-  x *= 0x9E3779B1u;
-  x ^= hi;
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 
 struct TailArgs {
   const float* z;        // [G, W, 64]
@@ -64,13 +52,9 @@ __global__ __launch_bounds__(PN_WAVES * 64) void pointnet_tail_fwd_kernel(const 
       const int64_t row = g * W + w;
       float v = fmaxf(a.z[row * PN_C + lane], 0.f);
       if (a.seed != nullptr) {  // tbx_keyed_dropout on the [G * W, 64] view
-        const int64_t b = row / a.rows_per_scene;
-        const int64_t sc = b / a.time_batch;
-        const uint32_t ts = (uint32_t)(a.time0 + (int)(b - sc * a.time_batch));
-        const uint32_t krow = (uint32_t)(sc * a.rows_per_scene + (row - b * a.rows_per_scene));
-        const uint32_t lo = (uint32_t)sd ^ (a.site * 0x85EBCA6Bu) ^ (ts * 0x27D4EB2Fu);
-        const uint32_t hi = (uint32_t)(sd >> 32) + a.site * 0xC2B2AE35u + ts * 0x165667B1u;
-        v = mix(krow * (uint32_t)PN_C + (uint32_t)lane, lo, hi) >= a.thresh ? v * a.scale : 0.f;
+        const tbx_drop::RowKey rk = tbx_drop::row_key<int64_t>(row, a.rows_per_scene, a.time_batch, a.time0);
+        const tbx_drop::StreamKey sk = tbx_drop::stream_key(sd, a.site, rk.step);
+        v = tbx_drop::drop_mix(rk.scene_row * (uint32_t)PN_C + (uint32_t)lane, sk.lo, sk.hi) >= a.thresh ? v * a.scale : 0.f;
       }
       h[w] = v;
       if (!((inv >> w) & 1)) m = fmaxf(m, v);
@@ -218,10 +202,9 @@ extern "C" int tbx_pointnet_tail_fwd(const float* z, const uint8_t* invalid, int
   if (!shape_ok(n_groups, group_rows, cols)) return TBX_ERR_UNSUPPORTED;
   TailArgs a{z, invalid, out, n_groups, group_rows, nullptr, site, 0u, 1.0f, 1, 1, 0};
   if (p_drop > 0.f) {
-    if (!drop_seed || p_drop >= 1.f || rows_per_scene <= 0 || time_batch < 1 || time0 < 0) return TBX_ERR_ARG;
-    if ((n_groups * group_rows) % rows_per_scene) return TBX_ERR_ARG;
-    const double th = (double)p_drop * 4294967296.0;
-    a.seed = drop_seed, a.thresh = th < 1.0 ? 1u : (uint32_t)th, a.scale = 1.0f / (1.0f - p_drop);
+    if (p_drop >= 1.f || !tbx_drop::key_args_ok(drop_seed, n_groups * group_rows, rows_per_scene, time_batch, time0)) return TBX_ERR_ARG;
+    const tbx_drop::Rate r = tbx_drop::drop_rate(p_drop);
+    a.seed = drop_seed, a.thresh = r.thresh, a.scale = r.scale;
     a.rows_per_scene = rows_per_scene, a.time_batch = time_batch, a.time0 = time0;
   }
   if (group_rows <= 16) hipLaunchKernelGGL(pointnet_tail_fwd_kernel<16>, grid_of(n_groups), dim3(PN_WAVES * 64), 0, (hipStream_t)stream, a);
@@ -233,7 +216,7 @@ extern "C" int tbx_pointnet_tail_bwd(const float* dout, const float* out, const 
                                      float p_drop, float* dz, void* stream) {
   if (!dout || !out || !invalid || !dz || p_drop < 0.f || p_drop >= 1.f) return TBX_ERR_ARG;
   if (!shape_ok(n_groups, group_rows, cols)) return TBX_ERR_UNSUPPORTED;
-  TailBwdArgs a{dout, out, invalid, dz, n_groups, group_rows, p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f};
+  TailBwdArgs a{dout, out, invalid, dz, n_groups, group_rows, tbx_drop::drop_rate(p_drop).scale};
   if (group_rows <= 16) hipLaunchKernelGGL(pointnet_tail_bwd_kernel<16>, grid_of(n_groups), dim3(PN_WAVES * 64), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(pointnet_tail_bwd_kernel<32>, grid_of(n_groups), dim3(PN_WAVES * 64), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/tbx_hip.h"
+#include "drop_key.h"
 #include "tbx_common.h"
 
 namespace {
@@ -791,7 +792,7 @@ __device__ void op_elementwise(const tbx_stage_t& s, const Tile<MT, EXT>& t) {
     }
 }
 
-// tbx_keyed_dropout's mask (csrc/dropout.hip) applied in place to an LDS-resident block: time_batch = 1, so the key row is the
+// tbx_keyed_dropout's mask (drop_key.h) applied in place to an LDS-resident block: time_batch = 1, so the key row is the
 // chain's global row.
 template <int MT, bool EXT>
 __device__ void op_dropout(const tbx_stage_t& s, const Tile<MT, EXT>& t) {
@@ -800,23 +801,14 @@ __device__ void op_dropout(const tbx_stage_t& s, const Tile<MT, EXT>& t) {
   float* dst = t.b(s.dst) + s.dst_col;
   const int lds_d = t.l(s.dst);
   const int n = s.n;
-  const uint64_t sd = *(const TBX_GLOBAL uint64_t*)s.p0;
-  const uint32_t site = (uint32_t)s.div, ts = (uint32_t)s.k, thresh = (uint32_t)s.reserved;
-  const uint32_t lo = (uint32_t)sd ^ (site * 0x85EBCA6Bu) ^ (ts * 0x27D4EB2Fu);
-  const uint32_t hi = (uint32_t)(sd >> 32) + site * 0xC2B2AE35u + ts * 0x165667B1u;
+  const tbx_drop::StreamKey sk = tbx_drop::stream_key(*(const TBX_GLOBAL uint64_t*)s.p0, (uint32_t)s.div, (uint32_t)s.k);
+  const uint32_t thresh = (uint32_t)s.reserved;
   for (int r = wave; r < ROWS; r += nwave) {
     const uint32_t base = (uint32_t)(t.g0 + r) * (uint32_t)n;
     for (int c = lane; c < n; c += 64) {
-      uint32_t x = (base + (uint32_t)c) ^ lo;
-      x *= 0x9E3779B1u;
-      x ^= hi;
-      x ^= x >> 16;
-      x *= 0x7feb352du;
-      x ^= x >> 15;
-      x *= 0x846ca68bu;
-      x ^= x >> 16;
+      const bool keep = tbx_drop::drop_mix(base + (uint32_t)c, sk.lo, sk.hi) >= thresh;
       const float v = dst[r * lds_d + c];
-      dst[r * lds_d + c] = x >= thresh ? v * s.f0 : 0.f;
+      dst[r * lds_d + c] = keep ? v * s.f0 : 0.f;
     }
   }
 }

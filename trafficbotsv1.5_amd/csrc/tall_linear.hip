@@ -43,36 +43,15 @@ struct TallArgs {
   int rows_per_scene, time_batch, time0;
 };
 
-// tbx_keyed_dropout's mask (csrc/dropout.hip `mix`): the per-row part of the key (step of the row's batch entry, its row inside the scene)
-// once per row block, the per-element hash in the epilogue
+// tbx_keyed_dropout's mask of a lane's output row: the per-row part of the key once per row block (m < 2^31: 32-bit divisions),
+// the per-element hash in the epilogue
 struct TallRowKey {
-  uint32_t lo, hi, base;  // base = key row * n
+  tbx_drop::StreamKey sk;
+  uint32_t base;  // scene row * n
 };
 __device__ __forceinline__ TallRowKey tall_row_key(const TallArgs& a, const uint64_t sd, const uint32_t row) {
-  const uint32_t b = row / (uint32_t)a.rows_per_scene;  // (m < 2^31: 32-bit divisions)
-  const uint32_t sc = b / (uint32_t)a.time_batch;
-  const uint32_t ts = (uint32_t)a.time0 + (b - sc * (uint32_t)a.time_batch);
-  const uint32_t krow = sc * (uint32_t)a.rows_per_scene + (row - b * (uint32_t)a.rows_per_scene);
-  TallRowKey k;
-  k.lo = (uint32_t)sd ^ (a.drop_site * 0x85EBCA6Bu) ^ (ts * 0x27D4EB2Fu);
-  k.hi = (uint32_t)(sd >> 32) + a.drop_site * 0xC2B2AE35u + ts * 0x165667B1u;
-  k.base = krow * (uint32_t)a.n;
-  return k;
-}
-__device__ __forceinline__ f32x4 tall_drop4(const TallArgs& a, const TallRowKey& k, const int c, f32x4 v) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    uint32_t x = (k.base + (uint32_t)(c + r)) ^ k.lo;
-    x *= 0x9E3779B1u;
-    x ^= k.hi;
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    v[r] = x >= a.drop_thresh ? v[r] * a.drop_scale : 0.f;
-  }
-  return v;
+  const tbx_drop::RowKey rk = tbx_drop::row_key<uint32_t>(row, a.rows_per_scene, a.time_batch, a.time0);
+  return {tbx_drop::stream_key(sd, a.drop_site, rk.step), rk.scene_row * (uint32_t)a.n};
 }
 
 __global__ __launch_bounds__(NT) void tall_linear_kernel(const TallArgs a) {
@@ -102,7 +81,7 @@ __global__ __launch_bounds__(NT) void tall_linear_kernel(const TallArgs a) {
   const uint64_t drop_sd = a.drop_thresh != 0u ? *(const TBX_GLOBAL uint64_t*)a.drop_seed : 0ull;
   TallRowKey rkey[4];  // the lane's 4 output rows (q * 16 + j) of the current row block
 #pragma unroll
-  for (int q = 0; q < 4; ++q) rkey[q] = a.drop_thresh != 0u ? tall_row_key(a, drop_sd, (uint32_t)(row_cur + q * 16 + j)) : TallRowKey{0u, 0u, 0u};
+  for (int q = 0; q < 4; ++q) rkey[q] = a.drop_thresh != 0u ? tall_row_key(a, drop_sd, (uint32_t)(row_cur + q * 16 + j)) : TallRowKey{{0u, 0u}, 0u};
   f32x4 xin[4];
   auto request_x = [&](int kc) {  // rows of the row block at xp, K chunk kc
 #pragma unroll
@@ -180,7 +159,7 @@ __global__ __launch_bounds__(NT) void tall_linear_kernel(const TallArgs a) {
           f32x4 v = acc[q].sum();
           if (a.has_bias) v += bias;
           if (a.relu) v = relu4(v);
-          if (a.drop_thresh != 0u) v = tall_drop4(a, rkey[q], c0, v);
+          if (a.drop_thresh != 0u) v = drop4(v, rkey[q].base + (uint32_t)c0, rkey[q].sk, a.drop_thresh, a.drop_scale);
           if (q * 16 + j < rows_cur) {
             *(TBX_GLOBAL f32x4*)(yo + q * y16) = v;
             if (yh != nullptr) *(TBX_GLOBAL u32x2*)(yh + nb * 128 + q * h16) = __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
@@ -237,10 +216,10 @@ static int tall_launch(const float* x, int64_t m, int k, int ldx, const float* i
   if (y16 != nullptr && (ldy16 < n || (ldy16 % 4) || (((uintptr_t)y16) & 7))) return TBX_ERR_ALIGN;
   TallArgs a{x, image, y, m, ldx, ldy, k, n, has_bias, relu, y16, ldy16, nullptr, 0u, 0u, 1.0f, 1, 1, 0};
   if (drop != nullptr && drop->p > 0.f) {
-    if (drop->p >= 1.f || !drop->seed || drop->rows_per_scene <= 0 || drop->time_batch < 1 || drop->time0 < 0 || m % drop->rows_per_scene) return TBX_ERR_ARG;
+    if (drop->p >= 1.f || !tbx_drop::key_args_ok(drop->seed, m, drop->rows_per_scene, drop->time_batch, drop->time0)) return TBX_ERR_ARG;
     if (m > 0x7fffffff) return TBX_ERR_UNSUPPORTED;  // (the mask's row arithmetic is 32-bit)
-    const double th = (double)drop->p * 4294967296.0;  // (tbx_keyed_dropout's threshold and scale)
-    a.drop_seed = drop->seed, a.drop_site = drop->site, a.drop_thresh = th < 1.0 ? 1u : (uint32_t)th, a.drop_scale = 1.0f / (1.0f - drop->p);
+    const tbx_drop::Rate r = tbx_drop::drop_rate(drop->p);
+    a.drop_seed = drop->seed, a.drop_site = drop->site, a.drop_thresh = r.thresh, a.drop_scale = r.scale;
     a.rows_per_scene = drop->rows_per_scene, a.time_batch = drop->time_batch, a.time0 = drop->time0;
   }
   static tbx::PerDeviceOnce lds_attr;  // (per device, thread-safe: tbx_common.h)

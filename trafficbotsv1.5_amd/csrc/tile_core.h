@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/tbx_hip.h"
+#include "drop_key.h"
 #include "tbx_common.h"
 
 // TBX_TILE_SINGLE (tile_layer / tile_heads / tile_window are compiled a second time with it: the *_bf16 entry points,
@@ -134,32 +135,23 @@ __device__ __forceinline__ void planes_write4(char* p, int row, int c, const f32
 #endif
 }
 
-// tbx_keyed_dropout's mask (csrc/dropout.hip, rowchain.hip op_dropout) on the lane's 4 consecutive columns [c, c + 4) of global
-// row `row` of an n-wide block: keep = hash(seed, site, step, row * n + column) >= thresh
+// tbx_keyed_dropout's mask (drop_key.h) on 4 consecutive counters [base, base + 4)
+__device__ __forceinline__ f32x4 drop4(f32x4 v, uint32_t base, const tbx_drop::StreamKey sk, uint32_t thresh, float scale) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = tbx_drop::drop_mix(base + (uint32_t)r, sk.lo, sk.hi) >= thresh ? v[r] * scale : 0.f;
+  return v;
+}
+// ... on the lane's 4 consecutive columns [c, c + 4) of global row `row` of an n-wide block (time_batch = 1: the scene row is the row)
 struct DropKey4 {
-  uint32_t lo, hi, thresh;
+  tbx_drop::StreamKey sk;
+  uint32_t thresh;
   float scale;
   __device__ __forceinline__ void init(const uint64_t* seed, uint32_t site, uint32_t step, uint32_t thresh_, float scale_) {
-    const uint64_t sd = *(const TBX_GLOBAL uint64_t*)seed;
-    lo = (uint32_t)sd ^ (site * 0x85EBCA6Bu) ^ (step * 0x27D4EB2Fu);
-    hi = (uint32_t)(sd >> 32) + site * 0xC2B2AE35u + step * 0x165667B1u;
+    sk = tbx_drop::stream_key(*(const TBX_GLOBAL uint64_t*)seed, site, step);
     thresh = thresh_, scale = scale_;
   }
   __device__ __forceinline__ f32x4 apply(f32x4 v, int64_t row, int c, int n) const {
-    const uint32_t base = (uint32_t)row * (uint32_t)n + (uint32_t)c;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      uint32_t x = (base + (uint32_t)r) ^ lo;
-      x *= 0x9E3779B1u;
-      x ^= hi;
-      x ^= x >> 16;
-      x *= 0x7feb352du;
-      x ^= x >> 15;
-      x *= 0x846ca68bu;
-      x ^= x >> 16;
-      v[r] = x >= thresh ? v[r] * scale : 0.f;
-    }
-    return v;
+    return drop4(v, (uint32_t)row * (uint32_t)n + (uint32_t)c, sk, thresh, scale);
   }
 };
 

@@ -15,7 +15,7 @@ from . import abi, hip_base
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
 from .abi import HEADER_PATH, LIB_PATH, load  # noqa: F401
 from .hip_base import *  # noqa: F401,F403  (Seg, stream_ptr, packed_weight / stacked_linear / padded_weight)
-from .hip_base import _attn_args, _check, _cptr, _ptr  # noqa: F401
+from .hip_base import _attn_args, _check, _cptr, _fill_drop, _ptr  # noqa: F401
 from .hip_chain import *  # noqa: F401,F403  (Chain, group_tile_rows)
 from .hip_rules import *  # noqa: F401,F403  (rule_tables, rule_check, rule_accumulate, filter_futures, womd_modes, pose_to_global)
 from .hip_train import *  # noqa: F401,F403  (the training entry points)
@@ -307,12 +307,7 @@ def _layer_tile_args(x, attn=None, ffn=None, proj=None, store_x: bool = True, dr
             assert kv16.shape == (x.shape[0], 256) and kv16.is_contiguous()
             a.kv16_out = _ptr(kv16, torch.bfloat16)
     if drop is not None:  # dict(p, seed int64[1] device tensor, step, sites = (attention residual, FFN hidden, FFN output) | None each)
-        th = drop["p"] * 4294967296.0
-        a.drop_thresh = 1 if 0 < th < 1 else int(th)
-        a.drop_scale = 1.0 / (1.0 - drop["p"])
-        a.drop_seed, a.drop_step = _ptr(drop["seed"], torch.int64), int(drop["step"])
-        for i, st in enumerate(drop["sites"]):
-            a.drop_site[i] = -1 if st is None else int(st)
+        _fill_drop(a, drop)
     if rider is not None:
         r = rider["out"].shape[0]
         for k in ("add", "out") + (("inp",) if rider.get("pose3") is None else ()):
@@ -358,13 +353,8 @@ def heads_tile(x, hd: dict):
         assert len(raw["images"]) == 7
         for i, im in enumerate(raw["images"]):
             a.raw_images[i] = _ptr(im, torch.float32)
-        dr = raw.get("drop")
-        if dr is not None:
-            th = dr["p"] * 4294967296.0
-            a.drop_thresh, a.drop_scale = (1 if 0 < th < 1 else int(th)), 1.0 / (1.0 - dr["p"])
-            a.drop_seed, a.drop_step = _ptr(dr["seed"], torch.int64), int(dr["step"])
-            for i, st in enumerate(dr["sites"]):
-                a.drop_site[i] = -1 if st is None else int(st)
+        if raw.get("drop") is not None:
+            _fill_drop(a, raw["drop"])
     else:
         a.navi_emb, a.latent_emb = _cptr(hd["navi_emb"], torch.float32), _cptr(hd["latent_emb"], torch.float32)
     a.navi_valid, a.latent_invalid = _cptr(hd["navi_valid"], torch.uint8), _cptr(hd["latent_invalid"], torch.uint8)
@@ -389,11 +379,7 @@ def _window_tile_args(attr, pe, row_invalid, in_images, pn_images, window: int, 
     a.out, a.window, a.n_groups = _ptr(out, torch.float32), int(window), out.shape[0]
     assert attr.shape[0] == out.shape[0] * window
     if drop is not None:  # dict(p, seed, step, sites = the three PointNet layers' dropout site ids): training's stepping pass
-        th = drop["p"] * 4294967296.0
-        a.drop_thresh, a.drop_scale = (1 if 0 < th < 1 else int(th)), 1.0 / (1.0 - drop["p"])
-        a.drop_seed, a.drop_step = _ptr(drop["seed"], torch.int64), int(drop["step"])
-        for i, st in enumerate(drop["sites"]):
-            a.drop_site[i] = int(st)
+        _fill_drop(a, drop)
     return a
 
 

@@ -6,6 +6,7 @@ import ctypes as C
 import os
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
@@ -31,6 +32,43 @@ def _cptr(t: Optional[torch.Tensor], dtype=None) -> Optional[int]:
     if t is not None and not t.is_contiguous():
         raise RuntimeError("tbx kernels need contiguous tensors")
     return _ptr(t, dtype)
+
+
+# ---- keyed dropout: the Python restatement of csrc/drop_key.h (the only one) --------------------------------------------------
+def drop_rate(p: float):
+    """drop_key.h drop_rate: (thresh, scale) of the float32 p that crosses the C ABI. The drop_thresh / drop_scale fields of the tile
+    structs and the row chain's dropout stage are filled from here, so that they draw the library-filled launches' mask."""
+    pf = np.float32(p)
+    if not pf > 0:
+        return 0, 1.0
+    th = float(pf) * 4294967296.0
+    return (1 if th < 1.0 else int(th)), float(np.float32(1.0) / (np.float32(1.0) - pf))
+
+
+def drop_stream_key(seed: int, site: int, step: int):
+    """drop_key.h stream_key -> (lo, hi)."""
+    sd, m32 = seed % (1 << 64), 0xFFFFFFFF
+    return ((sd & m32) ^ ((site * 0x85EBCA6B) & m32) ^ ((step * 0x27D4EB2F) & m32),
+            ((sd >> 32) + site * 0xC2B2AE35 + step * 0x165667B1) & m32)
+
+
+def drop_mix(counter, lo: int, hi: int):
+    """drop_key.h drop_mix over a numpy array of counters -> uint32 array."""
+    x = np.asarray(counter).astype(np.uint32)
+    with np.errstate(over="ignore"):
+        x = (x ^ np.uint32(lo)) * np.uint32(0x9E3779B1)
+        x = x ^ np.uint32(hi)
+        x = (x ^ (x >> np.uint32(16))) * np.uint32(0x7FEB352D)
+        x = (x ^ (x >> np.uint32(15))) * np.uint32(0x846CA68B)
+        return x ^ (x >> np.uint32(16))
+
+
+def _fill_drop(a, drop: dict) -> None:
+    """The drop_* fields of a tile struct from drop = dict(p, seed int64[1] device tensor, step, sites = site ids, None: not dropped)."""
+    a.drop_thresh, a.drop_scale = drop_rate(drop["p"])
+    a.drop_seed, a.drop_step = _ptr(drop["seed"], torch.int64), int(drop["step"])
+    for i, st in enumerate(drop["sites"]):
+        a.drop_site[i] = -1 if st is None else int(st)
 
 
 DEFERRED = None  # hip.defer(): the list that collects launch descriptors instead of launching them

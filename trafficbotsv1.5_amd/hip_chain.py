@@ -8,7 +8,7 @@ import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
 from .abi import load  # noqa: F401
-from .hip_base import _check, _cptr, _ptr, packed_weight, stream_ptr
+from .hip_base import _check, _cptr, _ptr, drop_rate, packed_weight, stream_ptr
 
 
 def group_tile_rows(group_rows: int, n_groups: int) -> int:
@@ -144,9 +144,8 @@ class Chain:
 
     def dropout(self, dst, dst_col, n, p: float, seed, site: int, step: int):
         """dst[:, dst_col:+n] in place with tbx_keyed_dropout's mask of (seed, site, step, global row, column of n)."""
-        th = p * 4294967296.0
-        th = 1 if 0 < th < 1 else int(th)
-        return self._add(op=OP_DROPOUT, dst=dst, dst_col=dst_col, n=n, k=int(step), div=int(site), f0=1.0 / (1.0 - p),
+        th, scale = drop_rate(p)
+        return self._add(op=OP_DROPOUT, dst=dst, dst_col=dst_col, n=n, k=int(step), div=int(site), f0=scale,
                          reserved=th - (1 << 32) if th >= (1 << 31) else th, p0=seed)
 
     def rowmask(self, dst, dst_col, n, mask=None, fill=0.0, row_div=0, valid_mask=False):

@@ -9,7 +9,7 @@ import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
 from .abi import load  # noqa: F401
-from .hip_base import Seg, _attn_args, _check, _cptr, _derived, _name, _ptr, packed_weight, stream_ptr
+from .hip_base import Seg, _attn_args, _check, _cptr, _derived, _name, _ptr, drop_mix, drop_rate, drop_stream_key, packed_weight, stream_ptr
 
 
 def keyed_dropout(x: torch.Tensor, p: float, seed: torch.Tensor, site: int, rows_per_scene: int, time_batch: int = 1,
@@ -314,29 +314,16 @@ def knarpe_attn_bwd_gather(qbuf, q_off: int, qt_off: int, rpe_k_bias, n_batch: i
 
 
 def dropout_keep_mask(seed: int, call: int, n_rows: int, k_tot: int, p: float, n_head: int = 4, step: int = 0) -> torch.Tensor:
-    """Host restatement of the kernels' counter-based mask (csrc/attn.hip DropKey): bool [n_rows, n_head, k_tot] - for tests
-    and for anyone who needs the mask a (seed, call) pair produces."""
+    """Host restatement of the attention kernels' mask (csrc/attn_core.h DropKey over csrc/drop_key.h): bool [n_rows, n_head, k_tot]
+    - for tests and for anyone who needs the mask a (seed, call) pair produces."""
     import numpy as np
 
-    sd = np.uint64(seed % (1 << 64))
-    m32 = np.uint64(0xFFFFFFFF)
-    lo = np.uint32(sd & m32) ^ np.uint32((call * 0x85EBCA6B) & 0xFFFFFFFF) ^ np.uint32((step * 0x27D4EB2F) & 0xFFFFFFFF)
-    hi = np.uint32((int((sd >> np.uint64(32)) & m32) + call * 0xC2B2AE35 + step * 0x165667B1) & 0xFFFFFFFF)
     row = np.arange(n_rows, dtype=np.uint32)[:, None, None]
     h = np.arange(n_head, dtype=np.uint32)[None, :, None]
     t = np.arange(k_tot, dtype=np.uint32)[None, None, :]
     with np.errstate(over="ignore"):
-        x = ((row * np.uint32(128) + t) * np.uint32(4) + h) ^ lo
-        x = x * np.uint32(0x9E3779B1)
-        x = x ^ hi
-        x = x ^ (x >> np.uint32(16))
-        x = x * np.uint32(0x7FEB352D)
-        x = x ^ (x >> np.uint32(15))
-        x = x * np.uint32(0x846CA68B)
-        x = x ^ (x >> np.uint32(16))
-    th = p * 4294967296.0
-    th = np.uint32(1 if 0 < th < 1 else int(th))
-    return torch.from_numpy(x >= th)
+        counter = (row * np.uint32(128) + t) * np.uint32(4) + h
+    return torch.from_numpy(drop_mix(counter, *drop_stream_key(seed, call, step)) >= np.uint32(drop_rate(p)[0]))
 
 
 def train_chain_fwd(args: TrainChainArgs, mean: torch.Tensor, stride_n: int, stride_t: int, t0: int, t1: int):
