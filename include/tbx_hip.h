@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define TBX_ABI_VERSION 5
+#define TBX_ABI_VERSION 6
 
 enum {
   TBX_OK = 0,
@@ -453,34 +453,50 @@ int tbx_front(const tbx_front_t* args /* host */, void* stream);
  * tbx_knarpe_dec_layer_pair the step runs on one queue). Same results as the two launches, bit for bit. */
 int tbx_front_pair(const tbx_front_t* agents /* host */, const tbx_front_t* lights /* host */, void* stream);
 
+/* An elementwise keyed dropout: y[row, c] = x[row, c] * keep / (1 - p), keep = hash(seed, site, step, scene row, c) >= p * 2^32, for a
+ * tensor viewed as [rows, cols] (replaces F.dropout at modules/mlp.py:60-61, transformer_rpe.py:56-60, 93-131 in training). The mask is
+ * its own backward's (the gradient takes the same mask). rows_per_scene rows per batch entry; batch entry b = row / rows_per_scene is
+ * step time0 + b % time_batch of scene b / time_batch (tbx_attn_t's time-batched calls), scene row = (b / time_batch) * rows_per_scene + row %
+ * rows_per_scene. `site` distinguishes the dropout sites of a step. With p > 0: p < 1, seed != NULL, rows_per_scene > 0 dividing rows,
+ * time_batch >= 1, time0 >= 0 (else TBX_ERR_ARG); p == 0: no dropout, the other fields are not looked at.
+ * The threshold and the scale come from the FLOAT p (csrc/drop_key.h, the one definition of the mask and of this rule):
+ *   th = (double)p * 4294967296.0;  threshold = th < 1 ? 1 : (uint32_t)th;  scale = 1.0f / (1.0f - p)   (float arithmetic)
+ * e.g. p = 0.1f -> 429496736 (not (uint32_t)(0.1 * 2^32) = 429496729). The drop_thresh / drop_scale fields of tbx_layer_tile_t,
+ * tbx_heads_tile_t and tbx_window_tile_t and a TBX_OP_DROPOUT stage's reserved / f0 must hold exactly these values for the p of the
+ * other launches of the same training step: only then are the masks equal. */
+typedef struct tbx_drop_args {
+  const uint64_t* seed; /* DEVICE memory, read by the kernels: a captured graph draws fresh masks when the host rewrites it */
+  float p;
+  uint32_t site;
+  int32_t rows_per_scene, time_batch, time0;
+  int32_t pad_;
+} tbx_drop_t;
+
 /* tbx_tall_linear: y [m, n] = x [m, k] W^T (+ b) (optionally relu) over very many rows - the forward / input-gradient products of
  * training's time-batched pass - on the split-bf16 matrix path (< 3e-5 of sum |x||w| per output): image = tbx_pack_weight_mfma32 of
  * W [n x k] (wt = 1 for a [k x n] weight: the input gradient dx = dy W), k and n multiples of 128 (<= 1024), ldx / ldy % 4 == 0,
  * 16-byte aligned. has_bias: add the image's bias. k or n = 64 mod 128 (the 64-wide PointNet layers, polyline_encoder.py:49-61): the
  * image is that of W zero-padded to the next multiples of 128; x rows hold k, y rows n valid columns (loads / stores masked). */
-int tbx_tall_linear(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, int relu, float* y, int ldy,
-                    void* stream);
+typedef struct tbx_linear_args {
+  const float *x, *image;
+  float* y;
+  /* optional second output: the same rows rounded to bfloat16, y16 [m, ldy16] (the K/V table of attention_rpe.py:92-98 in the element type
+   * tbx_knarpe_attn_fwd_mfma gathers fastest, written by the producing LINEAR instead of a conversion pass; the fp32 rows stay for the
+   * backward). NULL: none. ldy16 >= n, % 4 == 0, 8-byte aligned. */
+  uint16_t* y16;
+  int64_t m;
+  int32_t k, ldx, n, has_bias, relu, ldy, ldy16, pad_;
+  /* drop.p > 0: y = dropout(relu(x W^T + b)) in the same launch: the hidden activation of a transformer layer's FFN
+   * (transformer_rpe.py:119-131: linear1 -> relu -> dropout) / an MLP layer (mlp.py:56-61) over the time-batched rows; the mask is
+   * tbx_keyed_dropout's for the [m, n] output, so tbx_relu_drop_bwd reads relu' and the mask off y exactly as behind tbx_relu_drop_fwd.
+   * Bit-identical to relu = 1 followed by tbx_keyed_dropout. Needs relu (else TBX_ERR_ARG) and m < 2^31; with y16:
+   * TBX_ERR_UNSUPPORTED. drop.p == 0: none. */
+  tbx_drop_t drop;
+} tbx_linear_t;
+int tbx_tall_linear(const tbx_linear_t* args /* host */, void* stream);
 /* ... with ONE bf16 product per term (x and W rounded to bfloat16, fp32 accumulation; the lo halves of the image are not read):
  * F.linear under torch.autocast(bfloat16). Same image, same arguments. */
-int tbx_tall_linear_bf16(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, int relu, float* y, int ldy,
-                         void* stream);
-/* ... with a second output: the same rows rounded to bfloat16, y16 [m, ldy16] (the K/V table of attention_rpe.py:92-98 in the element type
- * tbx_knarpe_attn_fwd_mfma gathers fastest, written by the producing LINEAR instead of a conversion pass; the fp32 rows stay for the
- * backward). Both arithmetic classes. */
-int tbx_tall_linear_dual(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, int relu, float* y, int ldy,
-                         uint16_t* y16, int ldy16, void* stream);
-int tbx_tall_linear_dual_bf16(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, int relu, float* y, int ldy,
-                              uint16_t* y16, int ldy16, void* stream);
-/* y = dropout(relu(x W^T + b)) in the same launch: the hidden activation of a transformer layer's FFN (transformer_rpe.py:119-131:
- * linear1 -> relu -> dropout) / an MLP layer (mlp.py:56-61) over the time-batched rows; the mask is tbx_keyed_dropout's for the [m, n]
- * output (p_drop = 0: relu only), so tbx_relu_drop_bwd reads relu' and the mask off y exactly as behind tbx_relu_drop_fwd.
- * Bit-identical to tbx_tall_linear(relu = 1) followed by tbx_keyed_dropout. _bf16: one bf16 product per term. */
-int tbx_tall_linear_relu_drop(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, float* y, int ldy,
-                              float p_drop, const uint64_t* drop_seed, uint32_t site, int rows_per_scene, int time_batch, int time0,
-                              void* stream);
-int tbx_tall_linear_relu_drop_bf16(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, float* y, int ldy,
-                                   float p_drop, const uint64_t* drop_seed, uint32_t site, int rows_per_scene, int time_batch, int time0,
-                                   void* stream);
+int tbx_tall_linear_bf16(const tbx_linear_t* args /* host */, void* stream);
 
 /* Image for the tbx_*_tile kernels of W_g [n x k] (g < groups; stored [k x n] per group if wt), bias [groups * n] or NULL. k = 32, 64 or a multiple
  * of 128, n % 16 == 0. Size in floats (negative: error code). Layout: csrc/tile_layer.hip. */
@@ -503,33 +519,20 @@ int tbx_pack_weight_mfma32_multi(const tbx_pack_job_t* jobs /* host */, int n_jo
 int tbx_knn_inverse(const int32_t* idx, const uint8_t* invalid, int n_batch, int n_src, int k, int n_tgt, int tgt_batch_div,
                     int32_t* inv_ptr, int32_t* inv_list, void* stream);
 
-/* Elementwise dropout with the same kind of key (replaces F.dropout at modules/mlp.py:60-61, transformer_rpe.py:56-60,
- * 93-131 in training): y[row, c] = x[row, c] * keep / (1 - p), keep = hash(seed, site, step, scene row, c) >= p * 2^32.
- * x, y [rows, cols] contiguous (y may alias x); rows_per_scene rows per batch entry; batch entry b = row / rows_per_scene is
- * step time0 + b % time_batch of scene b / time_batch (tbx_attn_t's time-batched calls), scene row = (b / time_batch) * rows_per_scene + row %
- * rows_per_scene. Its own backward (the gradient takes the same mask). `site` distinguishes the dropout sites of a step.
- * The threshold and the scale come from the FLOAT p_drop (csrc/drop_key.h, the one definition of the mask and of this rule):
- *   th = (double)p_drop * 4294967296.0;  threshold = th < 1 ? 1 : (uint32_t)th;  scale = 1.0f / (1.0f - p_drop)   (float arithmetic)
- * e.g. p_drop = 0.1f -> 429496736 (not (uint32_t)(0.1 * 2^32) = 429496729). The drop_thresh / drop_scale fields of tbx_layer_tile_t,
- * tbx_heads_tile_t and tbx_window_tile_t and a TBX_OP_DROPOUT stage's reserved / f0 must hold exactly these values for the p_drop of the
- * other launches of the same training step: only then are the masks equal. */
-int tbx_keyed_dropout(const float* x, float* y, int64_t rows, int cols, int rows_per_scene, float p_drop,
-                      const uint64_t* drop_seed /* device */, uint32_t site, int time_batch, int time0, void* stream);
+/* The dropout `drop` describes (tbx_drop_t; NULL or a p that is not > 0, NaN included: TBX_ERR_ARG) on x, y [rows, cols] contiguous (y may alias x). */
+int tbx_keyed_dropout(const float* x, float* y, int64_t rows, int cols, const tbx_drop_t* drop /* host */, void* stream);
 
 /* The elementwise glue of a transformer layer over the time-batched rows, one pass per tensor (training; autograd of
  * transformer_rpe.py:93-131: masked_fill / dropout / add / masked_fill and relu / dropout, each an HBM pass of its own in aten).
- * The dropout is tbx_keyed_dropout's for the tensor's [rows, cols] view (p_drop = 0: none); cols % 4 == 0, 16-byte aligned.
+ * The dropout is tbx_keyed_dropout's for the tensor's [rows, cols] view (drop = NULL or p = 0: none); cols % 4 == 0, 16-byte aligned.
  *   tbx_residual_drop_fwd: out = zero_out[row] ? 0 : x + dropout(zero_y[row] ? 0 : y)   (zero_y / zero_out: u8 per row, may be NULL)
  *   tbx_residual_drop_bwd: dy = (zero_out | zero_y)[row] ? 0 : dout * mask / (1 - p); dx (may be NULL: then dx = dout) = zero_out[row] ? 0 : dout
  *   tbx_relu_drop_fwd:     h = dropout(relu(z));   tbx_relu_drop_bwd: dz = h > 0 ? dh / (1 - p) : 0 */
-int tbx_residual_drop_fwd(const float* x, const float* y, const uint8_t* zero_y, const uint8_t* zero_out, int64_t rows, int cols, float p_drop,
-                          const uint64_t* drop_seed /* device */, uint32_t site, int rows_per_scene, int time_batch, int time0, float* out,
-                          void* stream);
-int tbx_residual_drop_bwd(const float* dout, const uint8_t* zero_y, const uint8_t* zero_out, int64_t rows, int cols, float p_drop,
-                          const uint64_t* drop_seed /* device */, uint32_t site, int rows_per_scene, int time_batch, int time0, float* dy,
-                          float* dx, void* stream);
-int tbx_relu_drop_fwd(const float* z, int64_t rows, int cols, float p_drop, const uint64_t* drop_seed /* device */, uint32_t site,
-                      int rows_per_scene, int time_batch, int time0, float* h, void* stream);
+int tbx_residual_drop_fwd(const float* x, const float* y, const uint8_t* zero_y, const uint8_t* zero_out, int64_t rows, int cols,
+                          const tbx_drop_t* drop /* host */, float* out, void* stream);
+int tbx_residual_drop_bwd(const float* dout, const uint8_t* zero_y, const uint8_t* zero_out, int64_t rows, int cols,
+                          const tbx_drop_t* drop /* host */, float* dy, float* dx, void* stream);
+int tbx_relu_drop_fwd(const float* z, int64_t rows, int cols, const tbx_drop_t* drop /* host */, float* h, void* stream);
 int tbx_relu_drop_bwd(const float* dh, const float* h, int64_t rows, int cols, float p_drop, float* dz, void* stream);
 /* h [n_batch, n_a, n_m, cols] += pa [n_batch, n_a, cols] (per agent) + pm [n_batch, n_m, cols] (per polyline), then relu if `relu`, in
  * place and in one pass: the broadcast terms of NaviPredictor's first Linear over agent x polyline pairs (navigation.py:245-262 - the
@@ -587,16 +590,14 @@ int tbx_layernorm_bwd_add(const float* x, const float* dy, const float* gamma, c
  * written once.
  *   tbx_pointnet_tail_fwd: z [n_groups, group_rows, 64] = the layer's Linear output, invalid [n_groups, group_rows] u8 ->
  *     out [n_groups, group_rows, 128] = [h | max over the group's valid rows of h], invalid rows zeroed, h = dropout(relu(z)) with
- *     tbx_keyed_dropout's mask for the [n_groups * group_rows, 64] view (p_drop = 0: none; site / rows_per_scene / time_batch / time0
- *     as there).
+ *     tbx_keyed_dropout's mask for the [n_groups * group_rows, 64] view (drop = NULL or p = 0: none).
  *   tbx_pointnet_tail_bwd: dz from dout and the forward's `out` (the maximum's gradient split evenly among tied rows, as aten's
  *     amax backward does; relu' and the dropout mask are read off h > 0).
  *   tbx_masked_maxpool_fwd / _bwd: y [n_groups, 128] = max over the valid rows of x [n_groups, group_rows, 128] (0 for a group without
  *     one); dx from dy and x, ties split evenly.
  * cols must be 64 (tail) / 128 (pool): anything else is TBX_ERR_UNSUPPORTED. */
-int tbx_pointnet_tail_fwd(const float* z, const uint8_t* invalid, int64_t n_groups, int group_rows, int cols, float p_drop,
-                          const uint64_t* drop_seed /* device */, uint32_t site, int rows_per_scene, int time_batch, int time0, float* out,
-                          void* stream);
+int tbx_pointnet_tail_fwd(const float* z, const uint8_t* invalid, int64_t n_groups, int group_rows, int cols,
+                          const tbx_drop_t* drop /* host */, float* out, void* stream);
 int tbx_pointnet_tail_bwd(const float* dout, const float* out, const uint8_t* invalid, int64_t n_groups, int group_rows, int cols,
                           float p_drop, float* dz, void* stream);
 int tbx_masked_maxpool_fwd(const float* x, const uint8_t* invalid, int64_t n_groups, int group_rows, int cols, float* y, void* stream);

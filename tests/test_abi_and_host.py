@@ -25,7 +25,8 @@ def test_library_exports_every_declared_symbol(hip):
                          "tbx_rowchain", "tbx_rowchain_ex", "tbx_knarpe_attn_bwd", "tbx_agent_prep", "tbx_tl_prep", "tbx_map_prep", "tbx_sim_step"}
     for s in syms:
         assert hasattr(lib, s), s
-    assert lib.tbx_version() == 5
+    assert lib.tbx_version() == 6
+    assert len(syms) == 75
     assert lib.tbx_error_string(-2).decode().startswith("shape")
 
 
@@ -101,7 +102,8 @@ def test_ctypes_mirrors_have_the_layout_gcc_gives_the_header(hip, tmp_path):
     root = Path(__file__).resolve().parent.parent
     pairs = [("tbx_stage_t", hip.Stage), ("tbx_attn_seg_t", hip.AttnSeg), ("tbx_attn_t", hip.Attn), ("tbx_dec_mid_t", hip.DecMid), ("tbx_dec_layer_t", hip.DecLayer), ("tbx_heads_tail_t", hip.HeadsTail), ("tbx_knn_job_t", hip.KnnJob), ("tbx_pose_embed_job_t", hip.PoseEmbedJob), ("tbx_sim_state_t", hip.SimState),
              ("tbx_train_chain_t", hip.TrainChainArgs), ("tbx_rule_ctx_t", hip.RuleCtx), ("tbx_layer_tile_t", hip.LayerTile),
-             ("tbx_heads_tile_t", hip.HeadsTile), ("tbx_window_tile_t", hip.WindowTile), ("tbx_agent_prep_args_t", hip.AgentPrepArgs), ("tbx_front_t", hip.Front), ("tbx_tl_tail_t", hip.TlTail), ("tbx_pack_job_t", hip.PackJob)]
+             ("tbx_heads_tile_t", hip.HeadsTile), ("tbx_window_tile_t", hip.WindowTile), ("tbx_agent_prep_args_t", hip.AgentPrepArgs), ("tbx_front_t", hip.Front), ("tbx_tl_tail_t", hip.TlTail), ("tbx_pack_job_t", hip.PackJob),
+             ("tbx_drop_t", hip.Drop), ("tbx_linear_t", hip.Linear)]
     src = tmp_path / "sz.c"
     # ... and offsetof of every field (same names on both sides): runs of same-sized pointers keep sizeof when two fields swap
     fields = [(c, t, f[0]) for c, t in pairs for f in t._fields_]
@@ -171,7 +173,7 @@ def test_python_dropout_rule_equals_drop_key_header(hip, tmp_path):
 
 def test_new_entry_points_validate_arguments_without_a_gpu(hip):
     lib = hip.load()
-    assert lib.tbx_keyed_dropout(None, None, 4, 4, 2, 0.1, None, 0, 1, 0, None) == -1
+    assert lib.tbx_keyed_dropout(None, None, 4, 4, C.byref(hip.Drop(seed=None, p=0.1, site=0, rows_per_scene=2, time_batch=1, time0=0)), None) == -1
     assert lib.tbx_linear_wgrad_splits(0, 128, 128) == -1
     assert 1 <= lib.tbx_linear_wgrad_splits(2_000_000, 128, 128) <= 1024
     assert lib.tbx_linear_wgrad_splits(100, 128, 128) == 2  # at least 64 rows per split
@@ -256,6 +258,85 @@ def test_attention_entry_points_validate_their_argument_struct_without_a_gpu(hip
     assert bwd(args(coef=dp(23), inv_ptr=(C.c_void_p * 2)(dp(24), dp(25)), inv_list=(C.c_void_p * 2)(dp(26), None)), None) == ARG
     assert bwd(args(coef=dp(23), inv_ptr=(C.c_void_p * 2)(dp(24), dp(25)), inv_list=(C.c_void_p * 2)(dp(26), dp(27)), n_batch=3, seg1__batch_div=2),
                None) == ARG
+
+
+def test_dropout_and_tall_linear_structs_are_validated_without_a_gpu(hip):
+    """tbx_drop_t / tbx_linear_t calls that must be refused BEFORE any launch (placeholder device addresses, never dereferenced): the
+    rules the structs add, the shared key set-up (csrc/drop_key.h make_key) behind every entry point that takes a tbx_drop_t, and each of
+    the six positional tall-LINEAR call shapes (plain, dual, relu_drop; each also as _bf16) written as a struct, with the code the
+    positional entry point gave for the same bad input."""
+    lib = hip.load()
+    ARG, UNSUPPORTED, ALIGN = -1, -2, -3
+    dp = lambda i: 0x10000 * (i + 1)  # 16-byte aligned, distinct
+    drop = lambda **kw: hip.Drop(**{**dict(seed=dp(9), p=0.1, site=3, rows_per_scene=64, time_batch=1, time0=0), **kw})
+
+    def lin(drop_=None, **kw):  # a well-formed plain call (128 rows of 128 -> 128), then the changes
+        a = hip.Linear(**{**dict(x=dp(0), image=dp(1), y=dp(2), m=128, k=128, ldx=128, n=128, has_bias=1, relu=0, ldy=128), **kw})
+        if drop_ is not None:
+            a.drop = drop_
+        return C.byref(a)
+
+    for f in (lib.tbx_tall_linear, lib.tbx_tall_linear_bf16):
+        assert f(None, None) == ARG                                                  # a NULL struct
+        assert f(lin(drop(), relu=0), None) == ARG                                   # drop.p > 0 without relu
+        assert f(lin(drop(), relu=1, y16=dp(3), ldy16=128), None) == UNSUPPORTED     # drop.p > 0 with y16
+        assert f(lin(drop(p=1.0), relu=1), None) == ARG                              # p >= 1
+        assert f(lin(drop(p=1.5), relu=1), None) == ARG
+        assert f(lin(drop(rows_per_scene=48), relu=1), None) == ARG                  # rows % rows_per_scene != 0
+        # the plain shape (tbx_tall_linear, _bf16)
+        assert f(lin(x=None), None) == ARG
+        assert f(lin(m=0), None) == ARG
+        assert f(lin(k=100), None) == UNSUPPORTED
+        assert f(lin(n=1088), None) == UNSUPPORTED
+        assert f(lin(ldx=64), None) == ARG
+        assert f(lin(ldy=130), None) == ARG
+        assert f(lin(y=dp(2) + 4), None) == ALIGN
+        assert f(lin(k=100, y=dp(2) + 4), None) == UNSUPPORTED                       # (precedence: the shape before the alignment)
+        # the dual shape (tbx_tall_linear_dual, _bf16)
+        assert f(lin(y16=dp(3), ldy16=64), None) == ALIGN
+        assert f(lin(y16=dp(3), ldy16=130), None) == ALIGN
+        assert f(lin(y16=dp(3) + 4, ldy16=128), None) == ALIGN
+        assert f(lin(y16=dp(3), ldy16=128, ldx=64), None) == ARG                     # (precedence: the fp32 side first)
+        # the relu_drop shape (tbx_tall_linear_relu_drop, _bf16: relu = 1)
+        assert f(lin(drop(p=-0.5), relu=1), None) == ARG
+        assert f(lin(drop(p=-0.5), relu=1, k=100), None) == ARG                      # (precedence: p < 0 before everything else)
+        assert f(lin(drop(seed=None), relu=1), None) == ARG
+        assert f(lin(drop(time_batch=0), relu=1), None) == ARG
+        assert f(lin(drop(time0=-1), relu=1), None) == ARG
+        assert f(lin(drop(rows_per_scene=0), relu=1), None) == ARG
+        assert f(lin(drop(p=1.0), relu=1, k=100), None) == UNSUPPORTED               # (precedence: the shape before the key)
+        assert f(lin(drop(), relu=1, m=1 << 31, ldx=128), None) == UNSUPPORTED       # 32-bit row arithmetic under dropout ...
+        assert f(lin(drop(rows_per_scene=48), relu=1, m=1 << 31), None) == ARG       # ... after the key's own checks
+    # the entry points that take a tbx_drop_t: same key rules behind each one's own checks
+    x, y, o = dp(0), dp(1), dp(2)
+    bad_keys = (drop(p=1.0), drop(seed=None), drop(rows_per_scene=48), drop(rows_per_scene=0), drop(time_batch=0), drop(time0=-1))
+    for d in bad_keys:
+        assert lib.tbx_keyed_dropout(x, y, 128, 128, C.byref(d), None) == ARG
+        assert lib.tbx_residual_drop_fwd(x, y, None, None, 128, 128, C.byref(d), o, None) == ARG
+        assert lib.tbx_residual_drop_bwd(x, None, None, 128, 128, C.byref(d), y, o, None) == ARG
+        assert lib.tbx_relu_drop_fwd(x, 128, 128, C.byref(d), o, None) == ARG
+        assert lib.tbx_pointnet_tail_fwd(x, y, 8, 16, 64, C.byref(d), o, None) == ARG
+    neg = C.byref(drop(p=-0.5))
+    assert lib.tbx_keyed_dropout(x, y, 128, 128, None, None) == ARG                  # this call IS the dropout: no key, p <= 0
+    assert lib.tbx_keyed_dropout(x, y, 128, 128, C.byref(drop(p=0.0)), None) == ARG
+    assert lib.tbx_keyed_dropout(x, y, 128, 128, neg, None) == ARG
+    for seed in (dp(9), None):  # a NaN p is not > 0 either: refused, never a launch on the neutral key (whose seed is NULL)
+        assert lib.tbx_keyed_dropout(x, y, 128, 128, C.byref(drop(p=float("nan"), seed=seed)), None) == ARG
+    assert lib.tbx_keyed_dropout(x, y, 0, 128, C.byref(drop()), None) == 0            # an empty tensor, after a good key
+    assert lib.tbx_keyed_dropout(x, y, 0, 128, C.byref(drop(p=1.0)), None) == ARG
+    assert lib.tbx_residual_drop_fwd(x, y, None, None, 128, 128, neg, o, None) == ARG
+    assert lib.tbx_relu_drop_fwd(x, 128, 128, neg, o, None) == ARG
+    # the glue ops' own precedence: pointers, alignment, shape, an empty tensor, then the key
+    assert lib.tbx_relu_drop_fwd(None, 128, 128, C.byref(drop(p=1.0)), o, None) == ARG
+    assert lib.tbx_relu_drop_fwd(x + 4, 128, 126, C.byref(drop(p=1.0)), o, None) == ALIGN
+    assert lib.tbx_relu_drop_fwd(x, 128, 126, C.byref(drop(p=1.0)), o, None) == UNSUPPORTED
+    assert lib.tbx_relu_drop_fwd(x, 0, 128, C.byref(drop(p=1.0)), o, None) == 0
+    assert lib.tbx_relu_drop_fwd(x, 0, 128, None, o, None) == 0
+    assert lib.tbx_residual_drop_bwd(x, None, None, 128, 128, C.byref(drop(p=1.0)), y, o + 4, None) == ALIGN
+    # PointNet tail: pointers, the shape, then the key
+    assert lib.tbx_pointnet_tail_fwd(x, None, 8, 16, 64, C.byref(drop(p=1.0)), o, None) == ARG
+    assert lib.tbx_pointnet_tail_fwd(x, y, 8, 33, 64, C.byref(drop(p=1.0)), o, None) == UNSUPPORTED
+    assert lib.tbx_pointnet_tail_fwd(x, y, 8, 16, 64, C.byref(drop(rows_per_scene=24)), o, None) == ARG  # 128 rows % 24
 
 
 def test_group_tile_rows_picks_the_least_wasteful_tile(hip):

@@ -1039,7 +1039,7 @@ def test_tall_linear_bf16_vs_float64(tb, m, k, n, wt, bias):
     err = (y.double() - ref).abs()
     print(f"[tall linear bf16 vs float64] m={m} k={k} n={n}: max err / sum |x||w| {float((err / worst).max()):.3g}")
     assert float((err / worst).max()) < 2.0 ** -8 and float((err / worst).max()) > 1e-6
-    # the dual-output form (tbx_tall_linear_dual: the K/V tables' bfloat16 copy written by the producing launch): the same fp32 rows, and
+    # the dual-output form (tbx_linear_t.y16: the K/V tables' bfloat16 copy written by the producing launch): the same fp32 rows, and
     # their round-to-nearest-even bfloat16 values
     for cls in (True, False):
         y16 = torch.empty(m, n, dtype=torch.bfloat16, device=dev)
@@ -1222,7 +1222,7 @@ def test_attention_fold_kernels_equal_the_torch_algebra(tb):
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 @pytest.mark.parametrize("rows,k,n,nb,dropout", [(20480, 128, 512, 4, True), (16450, 128, 128, 1, True), (18000, 256, 128, 2, False)])
 def test_linear_relu_drop_one_launch_equals_two(tb, rows, k, n, nb, dropout, prec):
-    """train_ops.linear_relu_drop (tbx_tall_linear_relu_drop: LINEAR + relu + keyed dropout in the launch's epilogue; the FFN's hidden
+    """train_ops.linear_relu_drop (tbx_tall_linear with tbx_linear_t.drop: LINEAR + relu + keyed dropout in the launch's epilogue; the FFN's hidden
     activation / an MLP layer over the time-batched rows) against the two launches it replaces (TallLinearFn, then ReluDropFn): values and
     all three gradients bit-identical - the same products, the same keyed mask (site ids advance alike; row count not a multiple of 64,
     several scenes per batch, a time batch with an offset)."""

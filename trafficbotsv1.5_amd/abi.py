@@ -49,6 +49,18 @@ class Attn(C.Structure):
                 + [("p_drop", C.c_float), ("drop_call", C.c_uint32), ("time_batch", C.c_int32), ("time0", C.c_int32), ("pad_", C.c_int32)])
 
 
+class Drop(C.Structure):
+    """tbx_drop_t (include/tbx_hip.h): an elementwise keyed dropout. Filled by hip_base.drop_struct."""
+    _fields_ = [("seed", C.c_void_p), ("p", C.c_float), ("site", C.c_uint32), ("rows_per_scene", C.c_int32), ("time_batch", C.c_int32),
+                ("time0", C.c_int32), ("pad_", C.c_int32)]
+
+
+class Linear(C.Structure):
+    """tbx_linear_t (include/tbx_hip.h): the arguments of tbx_tall_linear / _bf16."""
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "image", "y", "y16")] + [("m", C.c_int64)]
+                + [(n, C.c_int32) for n in ("k", "ldx", "n", "has_bias", "relu", "ldy", "ldy16", "pad_")] + [("drop", Drop)])
+
+
 class KnnJob(C.Structure):
     """tbx_knn_job_t (include/tbx_hip.h)."""
     _fields_ = ([(n, C.c_void_p) for n in ("src_pose", "src_invalid", "tgt_pose", "tgt_invalid", "idx", "invalid", "rel_pose", "emb")]
@@ -221,16 +233,16 @@ def load():
     lib.tbx_knarpe_dec_layer.argtypes = [C.POINTER(DecLayer), vp]
     lib.tbx_knn_embed_multi.argtypes = [C.POINTER(KnnJob), i32, vp, vp, i32, vp]
     lib.tbx_knn_embed_multi_pe.argtypes = [C.POINTER(KnnJob), i32, vp, vp, i32, C.POINTER(PoseEmbedJob), vp]
-    lib.tbx_keyed_dropout.argtypes = [vp, vp, i64, i32, i32, f32, vp, C.c_uint32, i32, i32, vp]
+    lib.tbx_keyed_dropout.argtypes = [vp, vp, i64, i32, C.POINTER(Drop), vp]
     lib.tbx_linear_wgrad_splits.argtypes = [i64, i32, i32]
     lib.tbx_linear_wgrad.argtypes = [vp, i32, vp, i32, i64, i32, i32, vp, vp, vp, i32, vp]
     lib.tbx_linear_wgrad_bf16.argtypes = lib.tbx_linear_wgrad.argtypes
-    lib.tbx_residual_drop_fwd.argtypes = [vp, vp, vp, vp, i64, i32, C.c_float, vp, C.c_uint32, i32, i32, i32, vp, vp]
-    lib.tbx_residual_drop_bwd.argtypes = [vp, vp, vp, i64, i32, C.c_float, vp, C.c_uint32, i32, i32, i32, vp, vp, vp]
-    lib.tbx_relu_drop_fwd.argtypes = [vp, i64, i32, C.c_float, vp, C.c_uint32, i32, i32, i32, vp, vp]
+    lib.tbx_residual_drop_fwd.argtypes = [vp, vp, vp, vp, i64, i32, C.POINTER(Drop), vp, vp]
+    lib.tbx_residual_drop_bwd.argtypes = [vp, vp, vp, i64, i32, C.POINTER(Drop), vp, vp, vp]
+    lib.tbx_relu_drop_fwd.argtypes = [vp, i64, i32, C.POINTER(Drop), vp, vp]
     lib.tbx_relu_drop_bwd.argtypes = [vp, vp, i64, i32, C.c_float, vp, vp]
     lib.tbx_pair_bias_relu.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp]
-    lib.tbx_pointnet_tail_fwd.argtypes = [vp, vp, i64, i32, i32, C.c_float, vp, C.c_uint32, i32, i32, i32, vp, vp]
+    lib.tbx_pointnet_tail_fwd.argtypes = [vp, vp, i64, i32, i32, C.POINTER(Drop), vp, vp]
     lib.tbx_pointnet_tail_bwd.argtypes = [vp, vp, vp, i64, i32, i32, C.c_float, vp, vp]
     lib.tbx_masked_maxpool_fwd.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     lib.tbx_masked_maxpool_bwd.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
@@ -258,12 +270,8 @@ def load():
     lib.tbx_front.argtypes = [C.POINTER(Front), vp]
     lib.tbx_front_pair.argtypes = [C.POINTER(Front), C.POINTER(Front), vp]
     lib.tbx_knarpe_dec_layer_pair.argtypes = [C.POINTER(DecLayer), C.POINTER(DecLayer), vp]
-    lib.tbx_tall_linear.argtypes = [vp, C.c_int64, i32, i32, vp, i32, i32, i32, vp, i32, vp]
-    lib.tbx_tall_linear_bf16.argtypes = lib.tbx_tall_linear.argtypes
-    lib.tbx_tall_linear_dual.argtypes = [vp, C.c_int64, i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp]
-    lib.tbx_tall_linear_dual_bf16.argtypes = lib.tbx_tall_linear_dual.argtypes
-    lib.tbx_tall_linear_relu_drop.argtypes = [vp, C.c_int64, i32, i32, vp, i32, i32, vp, i32, f32, vp, C.c_uint32, i32, i32, i32, vp]
-    lib.tbx_tall_linear_relu_drop_bf16.argtypes = lib.tbx_tall_linear_relu_drop.argtypes
+    lib.tbx_tall_linear.argtypes = [C.POINTER(Linear), vp]
+    lib.tbx_tall_linear_bf16.argtypes = [C.POINTER(Linear), vp]
     lib.tbx_tl_tail_tile.argtypes = [vp, i64, C.POINTER(TlTail), vp]
     lib.tbx_tl_tail_tile_bf16.argtypes = lib.tbx_tl_tail_tile.argtypes
     lib.tbx_pack_weight_mfma32_size.argtypes = [i32, i32, i32]
@@ -292,11 +300,11 @@ def load():
     lib.tbx_attn_fold_fwd.argtypes = [vp] * 14
     lib.tbx_attn_fold_bwd.argtypes = [vp] * 19
     lib.tbx_rule_navi_check.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    for name in ("tbx_layer_tile", "tbx_heads_tile", "tbx_window_tile", "tbx_front", "tbx_tall_linear", "tbx_pack_weight_mfma32", "tbx_pack_weight_mfma32_multi", "tbx_pack_weight", "tbx_pack_weight_split", "tbx_pack_weight_gemv", "tbx_rowchain_live", "tbx_knarpe_dec_mid", "tbx_knarpe_dec_layer", "tbx_knn_embed_multi", "tbx_knn_embed_multi_pe", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd", "tbx_knarpe_attn_bwd", "tbx_keyed_dropout", "tbx_linear_wgrad_splits", "tbx_linear_wgrad", "tbx_linear_wgrad_bf16", "tbx_tall_linear_bf16", "tbx_tl_tail_tile", "tbx_tl_tail_tile_bf16", "tbx_tall_linear_dual", "tbx_tall_linear_dual_bf16", "tbx_layernorm_fwd", "tbx_layernorm_bwd_partials", "tbx_layernorm_bwd", "tbx_layernorm_bwd_add", "tbx_residual_drop_fwd", "tbx_residual_drop_bwd", "tbx_relu_drop_fwd", "tbx_relu_drop_bwd", "tbx_pair_bias_relu", "tbx_pointnet_tail_fwd", "tbx_pointnet_tail_bwd", "tbx_masked_maxpool_fwd", "tbx_masked_maxpool_bwd", "tbx_train_chain_fwd", "tbx_train_chain_fwd_windows", "tbx_train_chain_bwd", "tbx_knn_inverse", "tbx_rowchain", "tbx_rowchain_ex", "tbx_agent_prep", "tbx_tl_prep",
-                 "tbx_map_prep", "tbx_sim_step", "tbx_sim_step_parts", "tbx_sim_step_tl_prep", "tbx_rule_tables", "tbx_rule_grid", "tbx_rule_grid_cells", "tbx_rule_check", "tbx_rule_accumulate", "tbx_filter_futures", "tbx_rule_navi_check", "tbx_attn_fold_fwd", "tbx_attn_fold_bwd", "tbx_tall_linear_relu_drop", "tbx_tall_linear_relu_drop_bf16", "tbx_front_pair", "tbx_knarpe_dec_layer_pair",
+    for name in ("tbx_layer_tile", "tbx_heads_tile", "tbx_window_tile", "tbx_front", "tbx_tall_linear", "tbx_pack_weight_mfma32", "tbx_pack_weight_mfma32_multi", "tbx_pack_weight", "tbx_pack_weight_split", "tbx_pack_weight_gemv", "tbx_rowchain_live", "tbx_knarpe_dec_mid", "tbx_knarpe_dec_layer", "tbx_knn_embed_multi", "tbx_knn_embed_multi_pe", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd", "tbx_knarpe_attn_bwd", "tbx_keyed_dropout", "tbx_linear_wgrad_splits", "tbx_linear_wgrad", "tbx_linear_wgrad_bf16", "tbx_tall_linear_bf16", "tbx_tl_tail_tile", "tbx_tl_tail_tile_bf16", "tbx_layernorm_fwd", "tbx_layernorm_bwd_partials", "tbx_layernorm_bwd", "tbx_layernorm_bwd_add", "tbx_residual_drop_fwd", "tbx_residual_drop_bwd", "tbx_relu_drop_fwd", "tbx_relu_drop_bwd", "tbx_pair_bias_relu", "tbx_pointnet_tail_fwd", "tbx_pointnet_tail_bwd", "tbx_masked_maxpool_fwd", "tbx_masked_maxpool_bwd", "tbx_train_chain_fwd", "tbx_train_chain_fwd_windows", "tbx_train_chain_bwd", "tbx_knn_inverse", "tbx_rowchain", "tbx_rowchain_ex", "tbx_agent_prep", "tbx_tl_prep",
+                 "tbx_map_prep", "tbx_sim_step", "tbx_sim_step_parts", "tbx_sim_step_tl_prep", "tbx_rule_tables", "tbx_rule_grid", "tbx_rule_grid_cells", "tbx_rule_check", "tbx_rule_accumulate", "tbx_filter_futures", "tbx_rule_navi_check", "tbx_attn_fold_fwd", "tbx_attn_fold_bwd", "tbx_front_pair", "tbx_knarpe_dec_layer_pair",
                  "tbx_womd_modes", "tbx_pose_to_global", "tbx_rel_pose_dense", "tbx_diffbar_reward", "tbx_knarpe_attn_fwd_mfma"):
         getattr(lib, name).restype = C.c_int
-    if lib.tbx_version() != 5:
+    if lib.tbx_version() != 6:
         raise ImportError("libtbx_hip.so ABI version mismatch")
     # (an entry point without argtypes would get 64-bit handles - stream pointers under graph capture - as C ints)
     untyped = [s for s in declared_symbols() if getattr(lib, s).argtypes is None and s not in ("tbx_error_string", "tbx_version")]

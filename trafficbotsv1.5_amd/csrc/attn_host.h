@@ -50,7 +50,7 @@ inline int fill_common(A& a, const tbx_attn_t& t, int ldo, bool mfma) {
   return TBX_OK;
 }
 
-// The dropout fields of A from t's (drop_key.h: drop_rate). drop_thresh != 0 exactly when p_drop > 0.
+// The dropout fields of A from t's (drop_key.h: make_key). drop_thresh != 0 exactly when p_drop > 0.
 template <class A>
 inline int set_dropout(A& a, const tbx_attn_t& t) {
   a.drop_seed = t.drop_seed;
@@ -62,10 +62,11 @@ inline int set_dropout(A& a, const tbx_attn_t& t) {
   // (time_batch and time0 are held to their ranges without dropout too; the rows are n_batch whole scenes of n_src > 0 rows, which
   // fill_common has checked by now, so of the key's arguments only the seed can still be wrong)
   if (t.p_drop < 0.f || t.p_drop >= 1.f || t.time_batch < 1 || t.time0 < 0) return TBX_ERR_ARG;
-  if (t.p_drop > 0.f && !tbx_drop::key_args_ok(t.drop_seed, (int64_t)t.n_batch * t.n_src, t.n_src, t.time_batch, t.time0)) return TBX_ERR_ARG;
-  const tbx_drop::Rate r = tbx_drop::drop_rate(t.p_drop);
-  a.drop_thresh = r.thresh;
-  a.drop_scale = r.scale;
+  const tbx_drop_t d{t.drop_seed, t.p_drop, t.drop_call, t.n_src, t.time_batch, t.time0, 0};
+  tbx_drop::Key key;
+  if (const int rc = tbx_drop::make_key(&d, (int64_t)t.n_batch * t.n_src, &key)) return rc;
+  a.drop_thresh = key.thresh;
+  a.drop_scale = key.scale;
   return TBX_OK;
 }
 

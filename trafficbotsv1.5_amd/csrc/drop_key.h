@@ -1,13 +1,15 @@
-// Keyed dropout: the ONE definition of the mask (include/tbx_hip.h at tbx_keyed_dropout).
+// Keyed dropout: the ONE definition of the mask (include/tbx_hip.h at tbx_drop_t).
 //   keep(element) = drop_mix(counter, stream_key(seed, site, step)) >= thresh,   survivors scaled by `scale`
 // * stream key: (seed, site, step) -> (lo, hi); step and the scene row come from row_key(row, rows_per_scene, time_batch, time0):
 //   batch entry b = row / rows_per_scene is closed-loop step time0 + b % time_batch of scene b / time_batch.
 // * counter: the owner's layout - elementwise sites scene_row * cols + column, attention (scene_row * 128 + target slot) * 4 + head.
-// * (thresh, scale) from the float p: drop_rate, host only.
+// * (thresh, scale) from the float p: drop_rate, host only; a launch's whole key from its tbx_drop_t: make_key, host only.
 // Every kernel and every host set-up of the library goes through here, so a backward kernel in one file regenerates the mask a
 // forward kernel in another drew. Compiles under hipcc (device + host) and under a plain C++ compiler without HIP headers.
 #pragma once
 #include <stdint.h>
+
+#include "../../include/tbx_hip.h"  // (plain C: tbx_drop_t, the return codes)
 
 #ifdef __HIP__
 #define TBX_DROP_FN __host__ __device__ __attribute__((always_inline)) inline
@@ -58,12 +60,21 @@ TBX_DROP_FN RowKey row_key(I row, I b, int rows_per_scene, int time_batch, int t
   return {(uint32_t)time0 + (uint32_t)(b - sc * tb), (uint32_t)(sc * rps + (row - b * rps))};
 }
 
+// What a kernel holds of an elementwise site's key (by value, inside its argument struct). thresh == 0: no dropout - the neutral key
+// {NULL, 0, 0, 1.0f, 1, 1, 0}, whose seed is never read.
+struct Key {
+  const uint64_t* seed;  // device memory
+  uint32_t site, thresh;
+  float scale;
+  int rows_per_scene, time_batch, time0;
+};
+
 // ---- host side ----
 struct Rate {
   uint32_t thresh;  // drop when the hash < thresh; 0 exactly when p <= 0: no dropout
   float scale;      // 1 / (1 - p)
 };
-inline Rate drop_rate(float p) {  // p < 1: the caller's check
+inline Rate drop_rate(float p) {  // p < 1: make_key's check
   if (!(p > 0.f)) return {0u, 1.0f};
   const double th = (double)p * 4294967296.0;
   return {th < 1.0 ? 1u : (uint32_t)th, 1.0f / (1.0f - p)};
@@ -71,6 +82,35 @@ inline Rate drop_rate(float p) {  // p < 1: the caller's check
 // the key's arguments of a launch that drops (p > 0) over `rows` rows
 inline bool key_args_ok(const uint64_t* seed, int64_t rows, int rows_per_scene, int time_batch, int time0) {
   return seed != nullptr && rows_per_scene > 0 && time_batch >= 1 && time0 >= 0 && rows % rows_per_scene == 0;
+}
+
+// 1 / (1 - p) alone: a backward that reads the mask off the forward's output (tbx_relu_drop_bwd, tbx_pointnet_tail_bwd)
+inline float keep_scale(float p) { return drop_rate(p).scale; }
+
+// The key of a launch over `rows` rows from the caller's tbx_drop_t: the ONE host set-up. Return codes, in this order:
+//   1. d == NULL, or d->p is not > 0   -> TBX_OK, the neutral key; no other field of d is looked at
+//   2. d->p >= 1, or !key_args_ok(..)  -> TBX_ERR_ARG
+//   3. otherwise                       -> TBX_OK, (thresh, scale) = drop_rate(d->p)
+// Where that sits in each caller (the first check that fails decides; this is the only place the order is written down):
+//   tbx_tall_linear(_bf16)                   args == NULL or p < 0 -> ARG; x / image / y == NULL or m <= 0 -> ARG; k, n not multiples of
+//                                            64 in 64 .. 1024 -> UNSUPPORTED; ldx < k, ldy < n, ldx or ldy % 4 -> ARG; x / y / image not
+//                                            16-byte aligned -> ALIGN; y16 with ldy16 < n, ldy16 % 4 or not 8-byte aligned -> ALIGN;
+//                                            p > 0 without relu -> ARG; p > 0 with y16 -> UNSUPPORTED (no caller, the kernel path is
+//                                            untested); the key; p > 0 and m > 0x7fffffff -> UNSUPPORTED (its row arithmetic is 32-bit)
+//   tbx_residual_drop_*, tbx_relu_drop_fwd   pointers -> ARG; alignment -> ALIGN; rows < 0, cols <= 0 or cols % 4 -> UNSUPPORTED;
+//                                            rows == 0 -> OK; p < 0 -> ARG; the key
+//   tbx_keyed_dropout                        pointers, rows < 0, cols <= 0, d == NULL or p not > 0 -> ARG (this call IS the dropout);
+//                                            the key; rows == 0 -> OK
+//   tbx_pointnet_tail_fwd                    pointers -> ARG; the shape -> UNSUPPORTED; the key (p < 0 is "none", as it always was)
+//   tbx_knarpe_attn_* (tbx_attn_t)           after fill_common: p < 0, p >= 1, time_batch < 1, time0 < 0 -> ARG with or without
+//                                            dropout; the key
+inline int make_key(const tbx_drop_t* d, int64_t rows, Key* out) {
+  *out = Key{nullptr, 0u, 0u, 1.0f, 1, 1, 0};
+  if (d == nullptr || !(d->p > 0.f)) return TBX_OK;
+  if (d->p >= 1.f || !key_args_ok(d->seed, rows, d->rows_per_scene, d->time_batch, d->time0)) return TBX_ERR_ARG;
+  const Rate r = drop_rate(d->p);
+  *out = Key{d->seed, d->site, r.thresh, r.scale, d->rows_per_scene, d->time_batch, d->time0};
+  return TBX_OK;
 }
 
 }  // namespace tbx_drop

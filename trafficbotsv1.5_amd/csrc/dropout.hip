@@ -1,4 +1,4 @@
-// Keyed elementwise dropout (tbx_keyed_dropout, include/tbx_hip.h): the training path's replacement of F.dropout
+// Keyed elementwise dropout (tbx_keyed_dropout on a tbx_drop_t, include/tbx_hip.h): the training path's replacement of F.dropout
 // (reference: modules/mlp.py:60-61, transformer_rpe.py:56-60,93-131). The mask is a counter-based hash of (seed, site,
 // step, scene row, column), so a time-batched evaluation of T closed-loop steps draws exactly the masks of T per-step
 // calls, the backward regenerates the forward's mask, and a captured graph draws fresh masks when the host rewrites the
@@ -13,6 +13,13 @@
 namespace {
 
 using namespace tbx_drop;
+
+// DropArgs / GlueArgs keep the key's fields in their own order (embedding Key moved the kernels' scalar loads): filled from it here
+template <class A>
+inline void set_key(A& a, const Key& k) {
+  a.seed = k.seed, a.site = k.site, a.thresh = k.thresh, a.scale = k.scale;
+  a.rows_per_scene = k.rows_per_scene, a.time_batch = k.time_batch, a.time0 = k.time0;
+}
 
 struct DropArgs {
   const float* x;
@@ -130,19 +137,14 @@ __global__ __launch_bounds__(256) void glue_kernel(const GlueArgs a) {
   }
 }
 
-int glue_launch(int mode, GlueArgs a, float p_drop, const uint64_t* drop_seed, uint32_t site, int rows_per_scene, int time_batch,
-                int time0, void* stream) {
+// (the caller has checked its pointers and their alignment; the order of the checks: drop_key.h at make_key)
+int glue_launch(int mode, GlueArgs a, const tbx_drop_t* drop, void* stream) {
   if (a.rows < 0 || a.cols <= 0 || (a.cols & 3)) return TBX_ERR_UNSUPPORTED;
   if (a.rows == 0) return TBX_OK;
-  if (p_drop < 0.f || p_drop >= 1.f) return TBX_ERR_ARG;
-  a.seed = drop_seed, a.site = site, a.thresh = 0u, a.scale = 1.0f;
-  a.rows_per_scene = 1, a.time_batch = 1, a.time0 = 0;
-  if (p_drop > 0.f) {  // (p == 0 is "no dropout" here: the key's arguments are then not looked at)
-    if (!key_args_ok(drop_seed, a.rows, rows_per_scene, time_batch, time0)) return TBX_ERR_ARG;
-    const Rate r = drop_rate(p_drop);
-    a.thresh = r.thresh, a.scale = r.scale;
-    a.rows_per_scene = rows_per_scene, a.time_batch = time_batch, a.time0 = time0;
-  }
+  if (drop != nullptr && drop->p < 0.f) return TBX_ERR_ARG;
+  Key key;
+  if (const int rc = make_key(drop, a.rows, &key)) return rc;
+  set_key(a, key);
   const int64_t total = a.rows * (a.cols / 4);
   const int64_t want = (total + 255) / 256;
   const dim3 grid((unsigned)(want < 16384 ? want : 16384));
@@ -161,29 +163,26 @@ inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 }  // namespace
 
 extern "C" int tbx_residual_drop_fwd(const float* x, const float* y, const uint8_t* zero_y, const uint8_t* zero_out, int64_t rows, int cols,
-                                     float p_drop, const uint64_t* drop_seed, uint32_t site, int rows_per_scene, int time_batch, int time0,
-                                     float* out, void* stream) {
+                                     const tbx_drop_t* drop, float* out, void* stream) {
   if (!x || !y || !out) return TBX_ERR_ARG;
   if (!aligned16(x) || !aligned16(y) || !aligned16(out)) return TBX_ERR_ALIGN;
   GlueArgs a{x, y, zero_y, zero_out, out, nullptr, rows, cols};
-  return glue_launch(0, a, p_drop, drop_seed, site, rows_per_scene, time_batch, time0, stream);
+  return glue_launch(0, a, drop, stream);
 }
 
-extern "C" int tbx_residual_drop_bwd(const float* dout, const uint8_t* zero_y, const uint8_t* zero_out, int64_t rows, int cols, float p_drop,
-                                     const uint64_t* drop_seed, uint32_t site, int rows_per_scene, int time_batch, int time0, float* dy,
-                                     float* dx, void* stream) {
+extern "C" int tbx_residual_drop_bwd(const float* dout, const uint8_t* zero_y, const uint8_t* zero_out, int64_t rows, int cols,
+                                     const tbx_drop_t* drop, float* dy, float* dx, void* stream) {
   if (!dout || !dy) return TBX_ERR_ARG;
   if (!aligned16(dout) || !aligned16(dy) || !aligned16(dx)) return TBX_ERR_ALIGN;
   GlueArgs a{dout, nullptr, zero_y, zero_out, dy, dx, rows, cols};
-  return glue_launch(1, a, p_drop, drop_seed, site, rows_per_scene, time_batch, time0, stream);
+  return glue_launch(1, a, drop, stream);
 }
 
-extern "C" int tbx_relu_drop_fwd(const float* z, int64_t rows, int cols, float p_drop, const uint64_t* drop_seed, uint32_t site,
-                                 int rows_per_scene, int time_batch, int time0, float* h, void* stream) {
+extern "C" int tbx_relu_drop_fwd(const float* z, int64_t rows, int cols, const tbx_drop_t* drop, float* h, void* stream) {
   if (!z || !h) return TBX_ERR_ARG;
   if (!aligned16(z) || !aligned16(h)) return TBX_ERR_ALIGN;
   GlueArgs a{nullptr, z, nullptr, nullptr, h, nullptr, rows, cols};
-  return glue_launch(2, a, p_drop, drop_seed, site, rows_per_scene, time_batch, time0, stream);
+  return glue_launch(2, a, drop, stream);
 }
 
 extern "C" int tbx_relu_drop_bwd(const float* dh, const float* h, int64_t rows, int cols, float p_drop, float* dz, void* stream) {
@@ -192,9 +191,7 @@ extern "C" int tbx_relu_drop_bwd(const float* dh, const float* h, int64_t rows, 
   if (cols <= 0 || (cols & 3) || rows < 0 || p_drop < 0.f || p_drop >= 1.f) return TBX_ERR_ARG;
   if (rows == 0) return TBX_OK;
   GlueArgs a{dh, h, nullptr, nullptr, dz, nullptr, rows, cols};
-  // the mask is read off h: only the scale of the dropout is needed here
-  a.seed = nullptr, a.site = 0, a.thresh = 0u, a.scale = drop_rate(p_drop).scale;
-  a.rows_per_scene = 1, a.time_batch = 1, a.time0 = 0;
+  set_key(a, Key{nullptr, 0u, 0u, keep_scale(p_drop), 1, 1, 0});  // the mask is read off h: the neutral key, with the scale of the dropout
   const int64_t total = rows * (cols / 4);
   const int64_t want = (total + 255) / 256;
   hipLaunchKernelGGL(glue_kernel<3>, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, (hipStream_t)stream, a);
@@ -238,16 +235,15 @@ extern "C" int tbx_pair_bias_relu(float* h, const float* pa, const float* pm, in
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 
-extern "C" int tbx_keyed_dropout(const float* x, float* y, int64_t rows, int cols, int rows_per_scene, float p_drop,
-                                 const uint64_t* drop_seed, uint32_t site, int time_batch, int time0, void* stream) {
-  if (!x || !y || rows < 0 || cols <= 0 || !key_args_ok(drop_seed, rows, rows_per_scene, time_batch, time0)) return TBX_ERR_ARG;
-  if (p_drop <= 0.f || p_drop >= 1.f) return TBX_ERR_ARG;  // (unlike the glue ops, p == 0 is an error: this call IS the dropout)
+extern "C" int tbx_keyed_dropout(const float* x, float* y, int64_t rows, int cols, const tbx_drop_t* drop, void* stream) {
+  // (every refusal is TBX_ERR_ARG. Unlike the glue ops, no key or a p that is not > 0 - NaN too - is an error: this call IS the
+  // dropout, and its kernel reads the seed without asking)
+  if (!x || !y || rows < 0 || cols <= 0 || drop == nullptr || !(drop->p > 0.f)) return TBX_ERR_ARG;
+  DropArgs a{x, y, rows, cols};
+  Key key;
+  if (const int rc = make_key(drop, rows, &key)) return rc;
+  set_key(a, key);
   if (rows == 0) return TBX_OK;
-  DropArgs a;
-  a.x = x, a.y = y, a.rows = rows, a.cols = cols, a.rows_per_scene = rows_per_scene, a.time_batch = time_batch, a.time0 = time0;
-  a.seed = drop_seed, a.site = site;
-  const Rate r = drop_rate(p_drop);
-  a.thresh = r.thresh, a.scale = r.scale;
   const bool vec = (cols % 4 == 0) && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
   const int64_t total = rows * (vec ? cols / 4 : cols);
   const int64_t want = (total + 255) / 256;

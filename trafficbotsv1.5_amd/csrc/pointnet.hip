@@ -24,10 +24,7 @@ struct TailArgs {
   float* out;            // [G, W, 128]
   int64_t G;
   int W;
-  const uint64_t* seed;  // NULL: no dropout
-  uint32_t site, thresh;
-  float scale;
-  int rows_per_scene, time_batch, time0;
+  tbx_drop::Key key;  // key.seed == NULL: no dropout
 };
 
 // bit w of the result: row w of group g is invalid (wave-uniform)
@@ -43,7 +40,7 @@ __global__ __launch_bounds__(PN_WAVES * 64) void pointnet_tail_fwd_kernel(const 
   if (g >= a.G) return;
   const int W = a.W;
   const uint32_t inv = invalid_bits(a.invalid, g, W, lane);
-  const uint64_t sd = a.seed != nullptr ? *a.seed : 0;
+  const uint64_t sd = a.key.seed != nullptr ? *a.key.seed : 0;
   float h[MAXW];
   float m = -INFINITY;
 #pragma unroll
@@ -51,10 +48,10 @@ __global__ __launch_bounds__(PN_WAVES * 64) void pointnet_tail_fwd_kernel(const 
     if (w < W) {
       const int64_t row = g * W + w;
       float v = fmaxf(a.z[row * PN_C + lane], 0.f);
-      if (a.seed != nullptr) {  // tbx_keyed_dropout on the [G * W, 64] view
-        const tbx_drop::RowKey rk = tbx_drop::row_key<int64_t>(row, a.rows_per_scene, a.time_batch, a.time0);
-        const tbx_drop::StreamKey sk = tbx_drop::stream_key(sd, a.site, rk.step);
-        v = tbx_drop::drop_mix(rk.scene_row * (uint32_t)PN_C + (uint32_t)lane, sk.lo, sk.hi) >= a.thresh ? v * a.scale : 0.f;
+      if (a.key.seed != nullptr) {  // tbx_keyed_dropout on the [G * W, 64] view
+        const tbx_drop::RowKey rk = tbx_drop::row_key<int64_t>(row, a.key.rows_per_scene, a.key.time_batch, a.key.time0);
+        const tbx_drop::StreamKey sk = tbx_drop::stream_key(sd, a.key.site, rk.step);
+        v = tbx_drop::drop_mix(rk.scene_row * (uint32_t)PN_C + (uint32_t)lane, sk.lo, sk.hi) >= a.key.thresh ? v * a.key.scale : 0.f;
       }
       h[w] = v;
       if (!((inv >> w) & 1)) m = fmaxf(m, v);
@@ -195,18 +192,12 @@ inline dim3 grid_of(int64_t G) { return dim3((unsigned)((G + PN_WAVES - 1) / PN_
 
 }  // namespace
 
-extern "C" int tbx_pointnet_tail_fwd(const float* z, const uint8_t* invalid, int64_t n_groups, int group_rows, int cols, float p_drop,
-                                     const uint64_t* drop_seed, uint32_t site, int rows_per_scene, int time_batch, int time0, float* out,
-                                     void* stream) {
+extern "C" int tbx_pointnet_tail_fwd(const float* z, const uint8_t* invalid, int64_t n_groups, int group_rows, int cols,
+                                     const tbx_drop_t* drop, float* out, void* stream) {
   if (!z || !invalid || !out) return TBX_ERR_ARG;
   if (!shape_ok(n_groups, group_rows, cols)) return TBX_ERR_UNSUPPORTED;
-  TailArgs a{z, invalid, out, n_groups, group_rows, nullptr, site, 0u, 1.0f, 1, 1, 0};
-  if (p_drop > 0.f) {
-    if (p_drop >= 1.f || !tbx_drop::key_args_ok(drop_seed, n_groups * group_rows, rows_per_scene, time_batch, time0)) return TBX_ERR_ARG;
-    const tbx_drop::Rate r = tbx_drop::drop_rate(p_drop);
-    a.seed = drop_seed, a.thresh = r.thresh, a.scale = r.scale;
-    a.rows_per_scene = rows_per_scene, a.time_batch = time_batch, a.time0 = time0;
-  }
+  TailArgs a{z, invalid, out, n_groups, group_rows, {}};
+  if (const int rc = tbx_drop::make_key(drop, n_groups * group_rows, &a.key)) return rc;  // (pointers, then the shape, then the key: drop_key.h)
   if (group_rows <= 16) hipLaunchKernelGGL(pointnet_tail_fwd_kernel<16>, grid_of(n_groups), dim3(PN_WAVES * 64), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(pointnet_tail_fwd_kernel<32>, grid_of(n_groups), dim3(PN_WAVES * 64), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
@@ -216,7 +207,7 @@ extern "C" int tbx_pointnet_tail_bwd(const float* dout, const float* out, const 
                                      float p_drop, float* dz, void* stream) {
   if (!dout || !out || !invalid || !dz || p_drop < 0.f || p_drop >= 1.f) return TBX_ERR_ARG;
   if (!shape_ok(n_groups, group_rows, cols)) return TBX_ERR_UNSUPPORTED;
-  TailBwdArgs a{dout, out, invalid, dz, n_groups, group_rows, tbx_drop::drop_rate(p_drop).scale};
+  TailBwdArgs a{dout, out, invalid, dz, n_groups, group_rows, tbx_drop::keep_scale(p_drop)};
   if (group_rows <= 16) hipLaunchKernelGGL(pointnet_tail_bwd_kernel<16>, grid_of(n_groups), dim3(PN_WAVES * 64), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(pointnet_tail_bwd_kernel<32>, grid_of(n_groups), dim3(PN_WAVES * 64), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;

@@ -35,12 +35,9 @@ struct TallArgs {
   int ldx, ldy, k, n, has_bias, relu;
   uint16_t* y16;  // optional second output: the same rows as bfloat16 [m, ldy16] (the K/V tables the matrix-core attention gathers)
   int ldy16;
-  // optional keyed dropout behind the relu (tbx_tall_linear_relu_drop: the FFN's hidden activation / an MLP layer's output as ONE
-  // launch instead of LINEAR + tbx_relu_drop_fwd): tbx_keyed_dropout's mask for the [m, n] tensor; drop_thresh == 0: none
-  const uint64_t* drop_seed;
-  uint32_t drop_site, drop_thresh;
-  float drop_scale;
-  int rows_per_scene, time_batch, time0;
+  // optional keyed dropout behind the relu (tbx_linear_t.drop: the FFN's hidden activation / an MLP layer's output as ONE launch
+  // instead of LINEAR + tbx_relu_drop_fwd): tbx_keyed_dropout's mask for the [m, n] tensor; drop.thresh == 0: none
+  tbx_drop::Key drop;
 };
 
 // tbx_keyed_dropout's mask of a lane's output row: the per-row part of the key once per row block (m < 2^31: 32-bit divisions),
@@ -50,8 +47,8 @@ struct TallRowKey {
   uint32_t base;  // scene row * n
 };
 __device__ __forceinline__ TallRowKey tall_row_key(const TallArgs& a, const uint64_t sd, const uint32_t row) {
-  const tbx_drop::RowKey rk = tbx_drop::row_key<uint32_t>(row, a.rows_per_scene, a.time_batch, a.time0);
-  return {tbx_drop::stream_key(sd, a.drop_site, rk.step), rk.scene_row * (uint32_t)a.n};
+  const tbx_drop::RowKey rk = tbx_drop::row_key<uint32_t>(row, a.drop.rows_per_scene, a.drop.time_batch, a.drop.time0);
+  return {tbx_drop::stream_key(sd, a.drop.site, rk.step), rk.scene_row * (uint32_t)a.n};
 }
 
 __global__ __launch_bounds__(NT) void tall_linear_kernel(const TallArgs a) {
@@ -78,10 +75,10 @@ __global__ __launch_bounds__(NT) void tall_linear_kernel(const TallArgs a) {
   int rows_req = (int)(a.m - (int64_t)blockIdx.x * ROWS);  // rows left from the requested row block on (may exceed 64)
   int rows_cur = rows_req;
   int64_t row_cur = (int64_t)blockIdx.x * ROWS;  // first global row of the row block being multiplied
-  const uint64_t drop_sd = a.drop_thresh != 0u ? *(const TBX_GLOBAL uint64_t*)a.drop_seed : 0ull;
+  const uint64_t drop_sd = a.drop.thresh != 0u ? *(const TBX_GLOBAL uint64_t*)a.drop.seed : 0ull;
   TallRowKey rkey[4];  // the lane's 4 output rows (q * 16 + j) of the current row block
 #pragma unroll
-  for (int q = 0; q < 4; ++q) rkey[q] = a.drop_thresh != 0u ? tall_row_key(a, drop_sd, (uint32_t)(row_cur + q * 16 + j)) : TallRowKey{{0u, 0u}, 0u};
+  for (int q = 0; q < 4; ++q) rkey[q] = a.drop.thresh != 0u ? tall_row_key(a, drop_sd, (uint32_t)(row_cur + q * 16 + j)) : TallRowKey{{0u, 0u}, 0u};
   f32x4 xin[4];
   auto request_x = [&](int kc) {  // rows of the row block at xp, K chunk kc
 #pragma unroll
@@ -159,7 +156,7 @@ __global__ __launch_bounds__(NT) void tall_linear_kernel(const TallArgs a) {
           f32x4 v = acc[q].sum();
           if (a.has_bias) v += bias;
           if (a.relu) v = relu4(v);
-          if (a.drop_thresh != 0u) v = drop4(v, rkey[q].base + (uint32_t)c0, rkey[q].sk, a.drop_thresh, a.drop_scale);
+          if (a.drop.thresh != 0u) v = drop4(v, rkey[q].base + (uint32_t)c0, rkey[q].sk, a.drop.thresh, a.drop.scale);
           if (q * 16 + j < rows_cur) {
             *(TBX_GLOBAL f32x4*)(yo + q * y16) = v;
             if (yh != nullptr) *(TBX_GLOBAL u32x2*)(yh + nb * 128 + q * h16) = __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(NT) void tall_linear_kernel(const TallArgs a) {
       if (next_rb) {
         yp += y_rb, rows_cur -= (int)gridDim.x * ROWS, row_cur += (int64_t)gridDim.x * ROWS;
         if (yh != nullptr) yh += h_rb;
-        if (a.drop_thresh != 0u) {
+        if (a.drop.thresh != 0u) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) rkey[q] = tall_row_key(a, drop_sd, (uint32_t)(row_cur + q * 16 + j));
         }
@@ -200,28 +197,21 @@ static int tall_cu_count() {
   return n;
 }
 
-struct TallDrop {
-  float p;
-  const uint64_t* seed;
-  uint32_t site;
-  int rows_per_scene, time_batch, time0;
-};
-
-static int tall_launch(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, int relu, float* y, int ldy,
-                       uint16_t* y16, int ldy16, void* stream, const TallDrop* drop = nullptr) {
-  if (x == nullptr || image == nullptr || y == nullptr || m <= 0) return TBX_ERR_ARG;
+// (the order of the checks and the code each gives: drop_key.h at make_key)
+extern "C" int TBX_TILE_ENTRY(tbx_tall_linear)(const tbx_linear_t* t, void* stream) {
+  if (t == nullptr || t->drop.p < 0.f) return TBX_ERR_ARG;
+  const int64_t m = t->m;
+  const int k = t->k, n = t->n;
+  if (t->x == nullptr || t->image == nullptr || t->y == nullptr || m <= 0) return TBX_ERR_ARG;
   if (k <= 0 || n <= 0 || (k % 64) || (n % 64) || k > 1024 || n > 1024) return TBX_ERR_UNSUPPORTED;
-  if (ldx < k || ldy < n || (ldx % 4) || (ldy % 4)) return TBX_ERR_ARG;
-  if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)image)) & 15) return TBX_ERR_ALIGN;
-  if (y16 != nullptr && (ldy16 < n || (ldy16 % 4) || (((uintptr_t)y16) & 7))) return TBX_ERR_ALIGN;
-  TallArgs a{x, image, y, m, ldx, ldy, k, n, has_bias, relu, y16, ldy16, nullptr, 0u, 0u, 1.0f, 1, 1, 0};
-  if (drop != nullptr && drop->p > 0.f) {
-    if (drop->p >= 1.f || !tbx_drop::key_args_ok(drop->seed, m, drop->rows_per_scene, drop->time_batch, drop->time0)) return TBX_ERR_ARG;
-    if (m > 0x7fffffff) return TBX_ERR_UNSUPPORTED;  // (the mask's row arithmetic is 32-bit)
-    const tbx_drop::Rate r = tbx_drop::drop_rate(drop->p);
-    a.drop_seed = drop->seed, a.drop_site = drop->site, a.drop_thresh = r.thresh, a.drop_scale = r.scale;
-    a.rows_per_scene = drop->rows_per_scene, a.time_batch = drop->time_batch, a.time0 = drop->time0;
-  }
+  if (t->ldx < k || t->ldy < n || (t->ldx % 4) || (t->ldy % 4)) return TBX_ERR_ARG;
+  if ((((uintptr_t)t->x) | ((uintptr_t)t->y) | ((uintptr_t)t->image)) & 15) return TBX_ERR_ALIGN;
+  if (t->y16 != nullptr && (t->ldy16 < n || (t->ldy16 % 4) || (((uintptr_t)t->y16) & 7))) return TBX_ERR_ALIGN;
+  if (t->drop.p > 0.f && !t->relu) return TBX_ERR_ARG;
+  if (t->drop.p > 0.f && t->y16 != nullptr) return TBX_ERR_UNSUPPORTED;
+  TallArgs a{t->x, t->image, t->y, m, t->ldx, t->ldy, k, n, t->has_bias, t->relu, t->y16, t->ldy16, {}};
+  if (const int rc = tbx_drop::make_key(&t->drop, m, &a.drop)) return rc;
+  if (a.drop.thresh != 0u && m > 0x7fffffff) return TBX_ERR_UNSUPPORTED;
   static tbx::PerDeviceOnce lds_attr;  // (per device, thread-safe: tbx_common.h)
   if (!lds_attr([&] { return !(hipFuncSetAttribute((const void*)tall_linear_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess); })) return TBX_ERR_LAUNCH;
   const int64_t n_rb = (m + ROWS - 1) / ROWS;
@@ -230,23 +220,4 @@ static int tall_launch(const float* x, int64_t m, int k, int ldx, const float* i
   const int grid_max = grid_env > 0 ? grid_env : tall_cu_count();
   hipLaunchKernelGGL(tall_linear_kernel, dim3((unsigned)(n_rb < grid_max ? n_rb : grid_max)), dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
-}
-
-extern "C" int TBX_TILE_ENTRY(tbx_tall_linear)(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, int relu, float* y, int ldy,
-                                               void* stream) {
-  return tall_launch(x, m, k, ldx, image, n, has_bias, relu, y, ldy, nullptr, 0, stream);
-}
-
-extern "C" int TBX_TILE_ENTRY(tbx_tall_linear_dual)(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, int relu, float* y,
-                                                    int ldy, uint16_t* y16, int ldy16, void* stream) {
-  if (y16 == nullptr) return TBX_ERR_ARG;
-  return tall_launch(x, m, k, ldx, image, n, has_bias, relu, y, ldy, y16, ldy16, stream);
-}
-
-extern "C" int TBX_TILE_ENTRY(tbx_tall_linear_relu_drop)(const float* x, int64_t m, int k, int ldx, const float* image, int n, int has_bias, float* y,
-                                                         int ldy, float p_drop, const uint64_t* drop_seed, uint32_t site, int rows_per_scene,
-                                                         int time_batch, int time0, void* stream) {
-  if (p_drop < 0.f) return TBX_ERR_ARG;
-  const TallDrop d{p_drop, drop_seed, site, rows_per_scene, time_batch, time0};
-  return tall_launch(x, m, k, ldx, image, n, has_bias, 1, y, ldy, nullptr, 0, stream, &d);
 }

@@ -19,7 +19,6 @@ from .hip_base import _attn_args, _check, _cptr, _fill_drop, _ptr  # noqa: F401
 from .hip_chain import *  # noqa: F401,F403  (Chain, group_tile_rows)
 from .hip_rules import *  # noqa: F401,F403  (rule_tables, rule_check, rule_accumulate, filter_futures, womd_modes, pose_to_global)
 from .hip_train import *  # noqa: F401,F403  (the training entry points)
-from .hip_train import _drop6  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ wrappers

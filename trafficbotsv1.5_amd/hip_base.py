@@ -71,6 +71,15 @@ def _fill_drop(a, drop: dict) -> None:
         a.drop_site[i] = -1 if st is None else int(st)
 
 
+def drop_struct(drop) -> Optional[Drop]:
+    """tbx_drop_t of drop = (p, seed int64[1] device tensor or None, site, rows_per_scene, time_batch, time0) - the only place that knows
+    the order; None (no dropout) stays None: the library's NULL."""
+    if drop is None:
+        return None
+    p, seed, site, rps, tb, t0 = drop
+    return Drop(_ptr(seed, torch.int64), float(p), int(site), int(rps), int(tb), int(t0))
+
+
 DEFERRED = None  # hip.defer(): the list that collects launch descriptors instead of launching them
 
 

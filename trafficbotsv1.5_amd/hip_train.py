@@ -9,7 +9,7 @@ import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
 from .abi import load  # noqa: F401
-from .hip_base import Seg, _attn_args, _check, _cptr, _derived, _name, _ptr, drop_mix, drop_rate, drop_stream_key, packed_weight, stream_ptr
+from .hip_base import Seg, _attn_args, _check, _cptr, _derived, _name, _ptr, drop_mix, drop_rate, drop_stream_key, drop_struct, packed_weight, stream_ptr
 
 
 def keyed_dropout(x: torch.Tensor, p: float, seed: torch.Tensor, site: int, rows_per_scene: int, time_batch: int = 1,
@@ -19,8 +19,7 @@ def keyed_dropout(x: torch.Tensor, p: float, seed: torch.Tensor, site: int, rows
     cols = x.shape[-1]
     rows = x.numel() // cols if cols else 0
     y = torch.empty_like(x) if out is None else out
-    rc = load().tbx_keyed_dropout(_ptr(x), _ptr(y), rows, cols, rows_per_scene, float(p), _ptr(seed, torch.int64), int(site),
-                                  int(time_batch), int(time0), stream_ptr())
+    rc = load().tbx_keyed_dropout(_ptr(x), _ptr(y), rows, cols, drop_struct((p, seed, site, rows_per_scene, time_batch, time0)), stream_ptr())
     _check(rc, "tbx_keyed_dropout")
     return y
 
@@ -57,8 +56,9 @@ def _make_pad128(w, b, npad, kpad):
 def tall_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, wt: bool = False, relu: bool = False,
                 bf16: bool = False, out: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None, drop=None) -> torch.Tensor:
     """y = x W^T (+ b) over many rows on the split-bf16 matrix path (tbx_tall_linear; bf16: ONE bf16 product per term,
-    tbx_tall_linear_bf16). wt: w is stored [k x n] (the input gradient dx = dy W of a Linear with weight W [n_out, n_in]: x = dy,
-    w = W, wt = True). drop (with relu): tbx_keyed_dropout's arguments - dropout(relu(.)) in the same launch."""
+    tbx_tall_linear_bf16; one tbx_linear_t either way). wt: w is stored [k x n] (the input gradient dx = dy W of a Linear with weight W [n_out, n_in]: x = dy,
+    w = W, wt = True). drop (with relu): tbx_keyed_dropout's arguments - dropout(relu(.)) in the same launch; together with out16 the
+    library refuses it (TBX_ERR_UNSUPPORTED: no kernel path for dropout beside the bfloat16 copy is tested)."""
     n, k = (w.shape[1], w.shape[0]) if wt else (w.shape[0], w.shape[1])
     x2 = x.reshape(-1, k)
     if x2.stride(1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
@@ -68,23 +68,16 @@ def tall_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = No
     y = torch.empty(x2.shape[0], n, dtype=torch.float32, device=x.device) if out is None else out
     # (out: rows may be a column block of a wider table - leading dimension a multiple of 4 floats, 16-byte aligned)
     assert y.shape == (x2.shape[0], n) and y.stride(1) == 1 and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0 and y.dtype == torch.float32
-    ldy = y.stride(0)
-    if out16 is not None:  # the same rows as bfloat16 as well (tbx_tall_linear_dual)
+    a = Linear(x=_ptr(x2, torch.float32), image=_ptr(img, torch.float32), y=_ptr(y), m=x2.shape[0], k=k, ldx=x2.stride(0), n=n,
+               has_bias=int(b is not None), relu=int(relu), ldy=y.stride(0))
+    if out16 is not None:  # the same rows as bfloat16 as well
         assert out16.shape == y.shape and out16.dtype == torch.bfloat16 and out16.is_contiguous()
-        fn = load().tbx_tall_linear_dual_bf16 if bf16 else load().tbx_tall_linear_dual
-        _check(fn(_ptr(x2, torch.float32), x2.shape[0], k, x2.stride(0), _ptr(img, torch.float32), n, int(b is not None), int(relu),
-                  _ptr(y), ldy, _ptr(out16, torch.bfloat16), n, stream_ptr()), "tbx_tall_linear_dual")
-        return y if out is not None else y.view(*x.shape[:-1], n)
-    if drop is not None:  # dropout(relu(.)) in the launch (tbx_tall_linear_relu_drop): drop = (p, seed, site, rows_per_scene, time_batch, time0)
+        a.y16, a.ldy16 = _ptr(out16, torch.bfloat16), n
+    if drop is not None:  # dropout(relu(.)) in the launch: drop = (p, seed, site, rows_per_scene, time_batch, time0)
         assert relu
-        p, seed, site, rps, tb, t0 = _drop6(drop)
-        fn = load().tbx_tall_linear_relu_drop_bf16 if bf16 else load().tbx_tall_linear_relu_drop
-        _check(fn(_ptr(x2, torch.float32), x2.shape[0], k, x2.stride(0), _ptr(img, torch.float32), n, int(b is not None), _ptr(y), ldy,
-                  p, seed, site, rps, tb, t0, stream_ptr()), "tbx_tall_linear_relu_drop")
-        return y if out is not None else y.view(*x.shape[:-1], n)
+        a.drop = drop_struct(drop)
     fn = load().tbx_tall_linear_bf16 if bf16 else load().tbx_tall_linear
-    _check(fn(_ptr(x2, torch.float32), x2.shape[0], k, x2.stride(0), _ptr(img, torch.float32), n, int(b is not None), int(relu),
-              _ptr(y), ldy, stream_ptr()), "tbx_tall_linear")
+    _check(fn(C.byref(a), stream_ptr()), "tbx_tall_linear")
     return y if out is not None else y.view(*x.shape[:-1], n)
 
 
@@ -133,52 +126,42 @@ def attn_fold_bwd(w, b, wr, br, wo, grads):
     return out
 
 
-NO_DROP = (0.0, None, 0, 1, 1, 0)  # (p, seed, site, rows_per_scene, time_batch, time0) of the glue ops without dropout
-
-
 def glue_ok(x: torch.Tensor) -> bool:
     """Tensors the one-pass glue kernels (tbx_residual_drop_*, tbx_relu_drop_*) take: fp32 on the device, last dimension % 4 == 0."""
     return x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and x.shape[-1] % 4 == 0 and x.numel() > 0
 
 
-def _drop6(drop):
-    p, seed, site, rps, tb, t0 = drop
-    return float(p), (_ptr(seed, torch.int64) if seed is not None else None), int(site), int(rps), int(tb), int(t0)
-
-
-def residual_drop_fwd(x, y, zero_y, zero_out, drop=NO_DROP):
-    """zero_out[row] ? 0 : x + dropout(zero_y[row] ? 0 : y); zero_* u8 per row or None."""
+def residual_drop_fwd(x, y, zero_y, zero_out, drop=None):
+    """zero_out[row] ? 0 : x + dropout(zero_y[row] ? 0 : y); zero_* u8 per row or None. drop = None or (p, seed int64[1] device tensor,
+    site, rows_per_scene, time_batch, time0), here and below."""
     assert glue_ok(x) and x.is_contiguous() and y.is_contiguous() and y.shape == x.shape and y.dtype == torch.float32
     cols = x.shape[-1]
     rows = x.numel() // cols
     for z in (zero_y, zero_out):
         assert z is None or (z.dtype == torch.uint8 and z.is_contiguous() and z.numel() == rows)
     out = torch.empty_like(x)
-    p, seed, site, rps, tb, t0 = _drop6(drop)
-    _check(load().tbx_residual_drop_fwd(_ptr(x), _ptr(y), _ptr(zero_y), _ptr(zero_out), rows, cols, p, seed, site, rps, tb, t0, _ptr(out),
-                                        stream_ptr()), "tbx_residual_drop_fwd")
+    _check(load().tbx_residual_drop_fwd(_ptr(x), _ptr(y), _ptr(zero_y), _ptr(zero_out), rows, cols, drop_struct(drop), _ptr(out), stream_ptr()),
+           "tbx_residual_drop_fwd")
     return out
 
 
-def residual_drop_bwd(dout, zero_y, zero_out, drop=NO_DROP):
+def residual_drop_bwd(dout, zero_y, zero_out, drop=None):
     """-> (dy, dx); dx is dout itself when there is no zero_out mask."""
     assert glue_ok(dout) and dout.is_contiguous()
     cols = dout.shape[-1]
     rows = dout.numel() // cols
     dy = torch.empty_like(dout)
     dx = torch.empty_like(dout) if zero_out is not None else None
-    p, seed, site, rps, tb, t0 = _drop6(drop)
-    _check(load().tbx_residual_drop_bwd(_ptr(dout), _ptr(zero_y), _ptr(zero_out), rows, cols, p, seed, site, rps, tb, t0, _ptr(dy), _ptr(dx),
-                                        stream_ptr()), "tbx_residual_drop_bwd")
+    _check(load().tbx_residual_drop_bwd(_ptr(dout), _ptr(zero_y), _ptr(zero_out), rows, cols, drop_struct(drop), _ptr(dy), _ptr(dx), stream_ptr()),
+           "tbx_residual_drop_bwd")
     return dy, (dx if dx is not None else dout)
 
 
-def relu_drop_fwd(z, drop=NO_DROP):
+def relu_drop_fwd(z, drop=None):
     assert glue_ok(z) and z.is_contiguous()
     cols = z.shape[-1]
     h = torch.empty_like(z)
-    p, seed, site, rps, tb, t0 = _drop6(drop)
-    _check(load().tbx_relu_drop_fwd(_ptr(z), z.numel() // cols, cols, p, seed, site, rps, tb, t0, _ptr(h), stream_ptr()), "tbx_relu_drop_fwd")
+    _check(load().tbx_relu_drop_fwd(_ptr(z), z.numel() // cols, cols, drop_struct(drop), _ptr(h), stream_ptr()), "tbx_relu_drop_fwd")
     return h
 
 
@@ -212,9 +195,7 @@ def pointnet_tail_fwd(z: torch.Tensor, invalid_u8: torch.Tensor, drop=None) -> t
     G, W, Cc = z.shape
     assert invalid_u8.numel() == G * W
     out = torch.empty(G, W, 2 * Cc, dtype=torch.float32, device=z.device)
-    p, seed, site, rps, tb, t0 = drop if drop is not None else (0.0, None, 0, 1, 1, 0)
-    _check(load().tbx_pointnet_tail_fwd(_ptr(z), _ptr(invalid_u8), G, W, Cc, float(p), _ptr(seed, torch.int64) if seed is not None else None,
-                                        int(site), int(rps), int(tb), int(t0), _ptr(out), stream_ptr()), "tbx_pointnet_tail_fwd")
+    _check(load().tbx_pointnet_tail_fwd(_ptr(z), _ptr(invalid_u8), G, W, Cc, drop_struct(drop), _ptr(out), stream_ptr()), "tbx_pointnet_tail_fwd")
     return out
 
 

@@ -100,7 +100,7 @@ def _tall_linear_backward(x, w, dy, has_b: bool, bf16: bool, needs):
 
 
 class TallLinearReluDropFn(torch.autograd.Function):
-    """h = dropout(relu(x W^T + b)) as ONE launch (tbx_tall_linear_relu_drop: the FFN's linear1 / an MLP layer over the time-batched
+    """h = dropout(relu(x W^T + b)) as ONE launch (tbx_tall_linear with tbx_linear_t.drop: the FFN's linear1 / an MLP layer over the time-batched
     rows) instead of TallLinearFn + ReluDropFn - the pre-activation is never written or read back. Backward: relu' and the mask are read
     off h (tbx_relu_drop_bwd), then TallLinearFn's products. Bit-identical to the two-launch form (tests/test_hip_training.py)."""
 
@@ -327,9 +327,10 @@ def _glue_ok(x: Tensor, p: float, training: bool) -> bool:
 
 
 def _drop_args(x: Tensor, p: float, training: bool):
-    """tbx_keyed_dropout's arguments for x [..., cols] with the id _drop would give this site (advances it), or hip.NO_DROP."""
+    """tbx_keyed_dropout's arguments (p, seed, site, rows_per_scene, time_batch, time0) for x [..., cols] with the id _drop would give this
+    site (advances it), or those of no dropout."""
     if not (training and p > 0):
-        return hip.NO_DROP
+        return (0.0, None, 0, 1, 1, 0)
     ST._DROP["site"] += 1
     rows = x.numel() // x.shape[-1]
     assert rows % ST._DROP["n_batch"] == 0

@@ -47,7 +47,7 @@ TALL_LINEAR = os.environ.get("TBX_TALL_LINEAR", "1") != "0"  # forward / input-g
 WGRAD_MIN_ROWS = int(os.environ.get("TBX_WGRAD_MIN_ROWS", "16384"))  # from here on dW = dY^T X is a reduction over so many rows that the library GEMM has 1-2 output tiles
 
 
-# K/V tables of the current training step that also exist as bfloat16 (made by the launch that made the fp32 rows: tbx_tall_linear_dual):
+# K/V tables of the current training step that also exist as bfloat16 (made by the launch that made the fp32 rows: tbx_linear_t.y16):
 # fp32 table's data_ptr -> (the fp32 table - kept alive, so the address stays its own -, the bfloat16 copy). None outside a step.
 _KV16: Optional[dict] = None
 
