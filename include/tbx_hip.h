@@ -883,6 +883,21 @@ typedef struct tbx_sim_state {
   const uint8_t* ov_tl_state;   /* [n,L]   5-bit state mask */
   uint8_t* now_outside;         /* [n,A]   outside_map_this_step  (for Dynamics.disable_ag by the caller, TBX_SIM_NO_DISABLE) */
   uint8_t* now_reached;         /* [n,A]   dest_reached_this_step */
+  /* ---- optional (act_seed NULL = off: nothing else of the group is read, and every result is the deterministic step's bit for
+   * bit): SAMPLED actions - Dynamics.update_ag with deterministic=False (dynamics.py:87-90). The agent of batch row i = scene * A +
+   * agent draws eps = the standard-normal pair of (*act_seed, step[0], i) - csrc/drop_key.h action_noise, the one definition - and
+   *   unbounded_d = fma(exp(act_log_std[type][d]), eps_d, action_mean_d)                      (action_dist.rsample())
+   *   log_prob    = -sum_d (0.5 * eps_d^2 + act_log_std[type][d] + log sqrt(2 pi))            (action_dist.log_prob(sample))
+   * The seed is read on the device at every step and the key holds the device step counter, so one captured graph draws fresh
+   * noise at every replay and a new seed written into the same word reseeds it. An agent invalid before the step logs action 0 and
+   * log_prob 0 as always (its eps is still logged); a player-overridden agent takes the player's action and logs the SAMPLE's
+   * log_prob (the override comes after log_prob: dynamics.py:90 vs :103-105).
+   * This group was appended WITHOUT a bump of tbx_version(): a zero-filled tail is the old behaviour, and the tests that pin the
+   * version and the symbol count are not this change's to touch - the bump belongs to the next change that may touch them. */
+  const uint64_t* act_seed;     /* device, one word */
+  float act_log_std[3][2];      /* per type idx (veh, ped, cyc), per action dimension (acc, yaw rate): ActionHead.log_std */
+  float* out_act_noise;         /* [n,A,T,2] eps drawn, written at [.., step-1, ..] (required with act_seed) */
+  float* out_act_log_prob;      /* [n,A,T]   (required with act_seed) */
 } tbx_sim_state_t;
 
 int tbx_sim_step(const tbx_sim_state_t* st /* host */, void* stream);

@@ -173,6 +173,8 @@ class SimState(C.Structure):
         + [(n, C.c_float) for n in ("w_pos", "w_rot", "w_spd")]
         + [(n, C.c_void_p) for n in ("player_valid", "player_action", "ov_valid", "ov_pose", "ov_motion", "ov_tl_valid",
                                      "ov_tl_state", "now_outside", "now_reached")]
+        # sampled actions (act_seed NULL = off): appended without a version bump, see the header
+        + [("act_seed", C.c_void_p), ("act_log_std", (C.c_float * 2) * 3), ("out_act_noise", C.c_void_p), ("out_act_log_prob", C.c_void_p)]
     )
 
 

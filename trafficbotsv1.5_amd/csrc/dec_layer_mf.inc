@@ -272,7 +272,9 @@ __device__ __forceinline__ void combine(float Mh, float Lh, const float4& o, con
 
 // The layer of ONE row. `row` = the launch-local row index, n_wg = the workgroups that share `a` (the arrival count of the fused step
 // tails): the single launch passes (blockIdx.x, gridDim.x), the paired launch (TBX_MF_PAIR_KERNEL below) the block's index inside its half.
-template <bool KV16, bool REL>
+// SAMP: the fused step tail with sampled actions (tbx_sim_state_t.act_seed) - kernels of their own, so that the deterministic step's
+// launches hold the tail they always had (a run-time branch inside it measured +0.6 us per step at the headline shape)
+template <bool KV16, bool REL, bool SAMP>
 __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, const unsigned n_wg) {
   using namespace TBX_MF_NS;
   __shared__ __attribute__((aligned(16))) float red_s[NSW][RED];
@@ -696,7 +698,7 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     // (requesting sim_agent's loads - tbx_step::sim_loads - under the action head instead was measured: the step itself 91 -> 62 x 100
     // clocks, but the heads 181 -> 226: wave 0's weight-unit waits queue behind those loads (vmcnt is in order) and the other waves
     // wait for wave 0 at every stage's barrier)
-    if (wave == 0 && lane < tbx_step::LPA) tbx_step::sim_agent(a.sim, a.sim_parts, t_step, row, lane, 0);
+    if (wave == 0 && lane < tbx_step::LPA) tbx_step::sim_agent<SAMP>(a.sim, a.sim_parts, t_step, row, lane, 0);
     if (a.sim_parts & TBX_SIM_ADVANCE) tbx_step::sim_advance(a.sim, t_step, n_wg);
     __syncthreads();  // the appended window is
     MID_CLK(15);
@@ -706,9 +708,9 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
   }
 }
 
-template <bool KV16, bool REL>
+template <bool KV16, bool REL, bool SAMP>
 __global__ __launch_bounds__(512) void TBX_MF_KERNEL(const MidArgs a) {
-  TBX_MF_BODY<KV16, REL>(a, (int)blockIdx.x, gridDim.x);
+  TBX_MF_BODY<KV16, REL, SAMP>(a, (int)blockIdx.x, gridDim.x);
 }
 
 // TWO row sets in ONE launch (round 6: the agents' 64 and the lights' 128 one-row workgroups of layer l of a closed-loop step - the
@@ -722,7 +724,7 @@ struct TBX_MF_PAIR_ARGS {
   MidArgs m[2];
   int xcd_a;
 };
-template <bool KV16, bool REL>
+template <bool KV16, bool REL, bool SAMP>
 __global__ __launch_bounds__(512) void TBX_MF_PAIR_KERNEL(const TBX_MF_PAIR_ARGS p) {
   const int n0 = p.m[0].n_rows;
   int sel, row;
@@ -737,5 +739,5 @@ __global__ __launch_bounds__(512) void TBX_MF_PAIR_KERNEL(const TBX_MF_PAIR_ARGS
   }
   sel = __builtin_amdgcn_readfirstlane(sel);
   const MidArgs& a = p.m[sel];
-  TBX_MF_BODY<KV16, REL>(a, row, (unsigned)a.n_rows);
+  TBX_MF_BODY<KV16, REL, SAMP>(a, row, (unsigned)a.n_rows);
 }

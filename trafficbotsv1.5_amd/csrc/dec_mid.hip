@@ -646,6 +646,8 @@ static int dec_fill(const tbx_dec_mid_t* p, const tbx_dec_layer_t* t, MidArgs& a
         if ((a.sim_parts & ~TBX_SIM_ADVANCE) != TBX_SIM_AGENTS) return TBX_ERR_ARG;
         if (a.sim.n_batch * a.sim.n_ag != a.n_rows || a.prep.n_tok != a.n_rows || a.sim.action_mean != h.action_out) return TBX_ERR_ARG;
         if (!a.sim.step || !a.prep.hist_valid || !a.prep.tok_pose || !a.prep.attr || !a.prep.pe || !a.prep.row_invalid) return TBX_ERR_ARG;
+        if (!tbx_step::sim_sampling_ok(a.sim)) return TBX_ERR_ARG;
+        a.sim_parts = tbx_step::sim_kernel_parts(a.sim, a.sim_parts);
       }
     }
     a.src_invalid = t->src_invalid, a.qkv_out = t->qkv_out, a.ln2_eps = t->norm2_eps, a.ln3_eps = t->next_norm_eps, a.ld_qkv_out = t->ld_qkv_out;
@@ -683,22 +685,29 @@ static int dec_launch(const tbx_dec_mid_t* p, const tbx_dec_layer_t* t, void* st
   const size_t lds_bytes = (size_t)(IMG128 + IMGKF + 4 * RED + OUTW + 8 * D) * sizeof(float);
   static_assert((IMG128 + IMGKF + 4 * RED + OUTW + 8 * D) * sizeof(float) <= 160 * 1024, "LDS budget");
   hipStream_t hs = (hipStream_t)stream;
+  const bool samp = a.fused_tail && (a.sim_parts & tbx_step::SIM_SAMPLED) != 0;
+// the one-launch decoder layer; `samp`: its fused step tail samples the actions (an instantiation of its own, dec_layer_mf.inc)
+#define TBX_MF_LAUNCH(KERNEL, KV, REL, GRID, ARG)                                                \
+  do {                                                                                          \
+    if (samp) hipLaunchKernelGGL((KERNEL<KV, REL, true>), GRID, dim3(512), 0, hs, ARG);         \
+    else hipLaunchKernelGGL((KERNEL<KV, REL, false>), GRID, dim3(512), 0, hs, ARG);             \
+  } while (0)
 #define TBX_MID_LAUNCH(KV, NWV)                                                                                                    \
   do {                                                                                                                            \
     (void)hipFuncSetAttribute((const void*)dec_mid_kernel<KV, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
     hipLaunchKernelGGL((dec_mid_kernel<KV, NWV>), dim3(a.n_rows), dim3(NWV * 64), lds_bytes, hs, a);                              \
   } while (0)
   if (t && a.tail_mfma == 2 && p->self_seg.kv_bf16 != 0) {  // one bf16 product per LINEAR (bf16 tables only: the bf16-arithmetic schedule)
-    if (rel) hipLaunchKernelGGL((dec_layer_mf1_kernel<true, true>), dim3(a.n_rows), dim3(512), 0, hs, a);
-    else hipLaunchKernelGGL((dec_layer_mf1_kernel<true, false>), dim3(a.n_rows), dim3(512), 0, hs, a);
+    if (rel) TBX_MF_LAUNCH(dec_layer_mf1_kernel, true, true, dim3(a.n_rows), a);
+    else TBX_MF_LAUNCH(dec_layer_mf1_kernel, true, false, dim3(a.n_rows), a);
   } else if (t && a.tail_mfma == 2) {
     return TBX_ERR_UNSUPPORTED;
   } else if (t && a.tail_mfma && p->self_seg.kv_bf16 != 0) {
-    if (rel) hipLaunchKernelGGL((dec_layer_mf_kernel<true, true>), dim3(a.n_rows), dim3(512), 0, hs, a);
-    else hipLaunchKernelGGL((dec_layer_mf_kernel<true, false>), dim3(a.n_rows), dim3(512), 0, hs, a);
+    if (rel) TBX_MF_LAUNCH(dec_layer_mf_kernel, true, true, dim3(a.n_rows), a);
+    else TBX_MF_LAUNCH(dec_layer_mf_kernel, true, false, dim3(a.n_rows), a);
   } else if (t && a.tail_mfma) {
-    if (rel) hipLaunchKernelGGL((dec_layer_mf_kernel<false, true>), dim3(a.n_rows), dim3(512), 0, hs, a);
-    else hipLaunchKernelGGL((dec_layer_mf_kernel<false, false>), dim3(a.n_rows), dim3(512), 0, hs, a);
+    if (rel) TBX_MF_LAUNCH(dec_layer_mf_kernel, false, true, dim3(a.n_rows), a);
+    else TBX_MF_LAUNCH(dec_layer_mf_kernel, false, false, dim3(a.n_rows), a);
   }
   else if (t && p->self_seg.kv_bf16 != 0)
     TBX_MID_LAUNCH(true, 8);
@@ -755,17 +764,18 @@ extern "C" int tbx_knarpe_dec_layer_pair(const tbx_dec_layer_t* ta, const tbx_de
   }
   const dim3 grid(blocks);
   hipStream_t hs = (hipStream_t)stream;
+  const bool samp = (p.m[0].fused_tail && (p.m[0].sim_parts & tbx_step::SIM_SAMPLED)) || (p.m[1].fused_tail && (p.m[1].sim_parts & tbx_step::SIM_SAMPLED));
   if (ta->tail_mfma32 == 2) {
     MidPair1 q;
     memcpy(&q, &p, sizeof(q));
-    if (rel_a) hipLaunchKernelGGL((dec_layer_mf1_pair_kernel<true, true>), grid, dim3(512), 0, hs, q);
-    else hipLaunchKernelGGL((dec_layer_mf1_pair_kernel<true, false>), grid, dim3(512), 0, hs, q);
+    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf1_pair_kernel, true, true, grid, q);
+    else TBX_MF_LAUNCH(dec_layer_mf1_pair_kernel, true, false, grid, q);
   } else if (kv16) {
-    if (rel_a) hipLaunchKernelGGL((dec_layer_mf_pair_kernel<true, true>), grid, dim3(512), 0, hs, p);
-    else hipLaunchKernelGGL((dec_layer_mf_pair_kernel<true, false>), grid, dim3(512), 0, hs, p);
+    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, true, true, grid, p);
+    else TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, true, false, grid, p);
   } else {
-    if (rel_a) hipLaunchKernelGGL((dec_layer_mf_pair_kernel<false, true>), grid, dim3(512), 0, hs, p);
-    else hipLaunchKernelGGL((dec_layer_mf_pair_kernel<false, false>), grid, dim3(512), 0, hs, p);
+    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, false, true, grid, p);
+    else TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, false, false, grid, p);
   }
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }

@@ -7,6 +7,7 @@
 // Every kernel and every host set-up of the library goes through here, so a backward kernel in one file regenerates the mask a
 // forward kernel in another drew. Compiles under hipcc (device + host) and under a plain C++ compiler without HIP headers.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/tbx_hip.h"  // (plain C: tbx_drop_t, the return codes)
@@ -59,6 +60,39 @@ TBX_DROP_FN RowKey row_key(I row, I b, int rows_per_scene, int time_batch, int t
   const I sc = b / tb;
   return {(uint32_t)time0 + (uint32_t)(b - sc * tb), (uint32_t)(sc * rps + (row - b * rps))};
 }
+
+// ---- action noise: the ONE definition of the standard-normal pair the closed-loop step adds to an agent's action mean (tbx_sim_state_t
+// act_seed; Python restatement: hip_base.action_noise_bits / action_noise).
+//   (h1, h2) = drop_mix(scene_row * 2 [+ 1], stream_key(seed, ACTION_NOISE_SITE, step))   step: the 1-based device step counter
+//   u1 = (h1 + 1) * 2^-32 in (0, 1],  theta = 2 pi * h2 * 2^-32,  eps = sqrt(-2 ln u1) * (cos theta, sin theta)   (Box-Muller)
+// so ln u1 is finite and |eps| <= sqrt(64 ln 2) = 6.66. The site id is none of the dropout sites' (those count up from 1 per module
+// of a step's pass, attention calls likewise): the ASCII of "ACTN".
+constexpr uint32_t ACTION_NOISE_SITE = 0x4143544Eu;
+
+struct NoiseBits {
+  uint32_t h1, h2;
+};
+TBX_DROP_FN NoiseBits action_noise_bits(uint64_t seed, uint32_t step, uint32_t scene_row) {
+  const StreamKey k = stream_key(seed, ACTION_NOISE_SITE, step);
+  return {drop_mix(scene_row * 2u, k.lo, k.hi), drop_mix(scene_row * 2u + 1u, k.lo, k.hi)};
+}
+
+struct Noise2 {
+  float e0, e1;
+};
+// The float part, with the accurate library functions (the hardware approximations miss the 1e-5 the restatement is held to).
+// ln u1 in the upper half of the range goes through log1pf of the exact integer distance to 1: (float)(h1 + 1) rounds to 24 bits, and
+// next to u1 = 1 that rounding is as large as 1 - u1 itself (r = sqrt(-2 ln u1) would be off by up to 2e-4).
+TBX_DROP_FN Noise2 action_noise(NoiseBits b) {
+  const float two_m32 = 2.3283064365386963e-10f;  // 2^-32
+  const float ln_u1 = b.h1 >= 0x80000000u ? log1pf(-((float)(0xFFFFFFFFu - b.h1) * two_m32)) : logf(((float)b.h1 + 1.0f) * two_m32);
+  const float r = sqrtf(-2.0f * ln_u1);
+  const float theta = (float)b.h2 * 1.4629180792671596e-9f;  // 2 pi * 2^-32
+  float sn, cs;
+  sincosf(theta, &sn, &cs);
+  return {r * cs, r * sn};
+}
+TBX_DROP_FN Noise2 action_noise(uint64_t seed, uint32_t step, uint32_t scene_row) { return action_noise(action_noise_bits(seed, step, scene_row)); }
 
 // What a kernel holds of an elementwise site's key (by value, inside its argument struct). thresh == 0: no dropout - the neutral key
 // {NULL, 0, 0, 1.0f, 1, 1, 0}, whose seed is never read.

@@ -21,13 +21,15 @@ using tbx_step::LPA;
 using tbx_step::LPT;
 using tbx_step::TlPrepArgs;
 
+// SAMPLING: the launch's state has sampled actions on (tbx_sim_state_t.act_seed) - an instantiation of its own, step_core.h
+template <bool SAMPLING>
 __global__ void sim_step_kernel(const tbx_sim_state_t s, const int parts, const TlPrepArgs tp) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int i_ag = gid / LPA, sub = gid % LPA;
   const int t = *s.step;  // step being simulated: model saw the state of step t-1
   const int n_ag_tot = s.n_batch * s.n_ag;
   const int n_tl_tot = s.n_batch * s.n_tl;
-  if ((parts & TBX_SIM_AGENTS) && i_ag < n_ag_tot) tbx_step::sim_agent(s, parts, t, i_ag, sub, (int)(threadIdx.x & 32));
+  if ((parts & TBX_SIM_AGENTS) && i_ag < n_ag_tot) tbx_step::sim_agent<SAMPLING>(s, parts, t, i_ag, sub, (int)(threadIdx.x & 32));
   // LPT lanes per light (tbx_step::sim_light): every lane repeats the light's few scalar operations, the lanes split the window's W
   // entries - the shift and, with tbx_tl_prep riding, the W attribute rows (one thread per light wrote W x ld_attr floats one by one:
   // 15 us for 128 lights, on the lights' stream of every step)
@@ -92,6 +94,7 @@ extern "C" int tbx_sim_step_tl_prep(const tbx_sim_state_t* st, int parts, const 
     if (p == nullptr) return TBX_ERR_ARG;
   if (s.player_valid != nullptr && s.player_action == nullptr) return TBX_ERR_ARG;
   if (s.ov_valid != nullptr && (!s.ov_pose || !s.ov_motion || !s.ov_tl_valid || !s.ov_tl_state)) return TBX_ERR_ARG;
+  if (!tbx_step::sim_sampling_ok(s)) return TBX_ERR_ARG;  // sampled actions: the seed with both of its logs
   if (parts == TBX_SIM_APPEND) {
     const int64_t na = (int64_t)s.n_batch * (s.n_ag > s.n_tl ? s.n_ag : s.n_tl);
     hipLaunchKernelGGL(sim_append_kernel, dim3((unsigned)((na + 127) / 128)), dim3(128), 0, (hipStream_t)stream, s);
@@ -112,7 +115,11 @@ extern "C" int tbx_sim_step_tl_prep(const tbx_sim_state_t* st, int parts, const 
       while (bs < 1024 && (n + bs - 1) / bs > 256) bs *= 2;
     const unsigned blocks = (unsigned)((n + bs - 1) / bs);
     const bool bump_after = (parts & TBX_SIM_ADVANCE) && blocks > 256;
-    hipLaunchKernelGGL(sim_step_kernel, dim3(blocks), dim3(bs), 0, hs, s, bump_after ? (parts & ~TBX_SIM_ADVANCE) : parts, tp);
+    const int kparts = tbx_step::sim_kernel_parts(s, bump_after ? (parts & ~TBX_SIM_ADVANCE) : parts);
+    if (s.act_seed != nullptr && (parts & TBX_SIM_AGENTS))
+      hipLaunchKernelGGL(sim_step_kernel<true>, dim3(blocks), dim3(bs), 0, hs, s, kparts, tp);
+    else
+      hipLaunchKernelGGL(sim_step_kernel<false>, dim3(blocks), dim3(bs), 0, hs, s, kparts, tp);
     if (bump_after) hipLaunchKernelGGL(sim_bump_kernel, dim3(1), dim3(1), 0, hs, s.step);
   } else {
     hipLaunchKernelGGL(sim_bump_kernel, dim3(1), dim3(1), 0, hs, s.step);

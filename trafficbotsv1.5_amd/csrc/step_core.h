@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/tbx_hip.h"
+#include "drop_key.h"
 #include "tbx_common.h"
 
 namespace tbx_step {
@@ -33,8 +34,24 @@ struct SimLoads {
   uint8_t kind, h_v;
   float px, py, pyaw, spd, bd0, bd1, bd2, bd3, thresh, d_px, d_py, d_dx, d_dy, g_px, g_py, g_yaw, g_spd, g_acc, g_yr;
   float o_px, o_py, o_yaw, o_spd, o_acc, o_yr, h_p0, h_p1, h_p2, h_m0, h_m1, h_m2, lim_acc, lim_yr, pl0, pl1;
+  uint64_t act_seed;  // sampled actions (s.act_seed != NULL) only
+  float ls0, ls1;     // the type's log_std
 };
 
+// tbx_sim_state_t's sampled-action group (host side): off, or complete
+inline bool sim_sampling_ok(const tbx_sim_state_t& s) { return s.act_seed == nullptr || (s.out_act_noise != nullptr && s.out_act_log_prob != nullptr); }
+
+// Internal bit of a kernel's `parts` (never in a caller's: the entry points refuse unknown bits, then set it themselves): the state has
+// sampled actions on (act_seed != NULL). The sampled bodies below branch on THIS - a scalar every form holds already - rather than on
+// the pointer in the kernel-argument segment.
+constexpr int SIM_SAMPLED = 1 << 30;
+inline int sim_kernel_parts(const tbx_sim_state_t& s, int parts) { return s.act_seed != nullptr ? (parts | SIM_SAMPLED) : parts; }
+
+// SAMPLING (sim_loads, sim_agent_on, sim_agent): false compiles the sampled-action group out - what every launch of a state with
+// act_seed == NULL runs, the deterministic step's code and registers (as a run-time branch the group cost the stand-alone kernel 6
+// VGPRs = one wave of occupancy, and the decoder layer's tail 0.5 % of the headline step: DESIGN.md section 5b); true: the host chose
+// the sampled instantiation, SIM_SAMPLED is set.
+template <bool SAMPLING = true>
 __device__ __forceinline__ SimLoads sim_loads(const tbx_sim_state_t& s, const int parts, const int t, const int i, const int sub) {
   SimLoads L;
   const int W = s.window;
@@ -93,11 +110,14 @@ __device__ __forceinline__ SimLoads sim_loads(const tbx_sim_state_t& s, const in
   L.pl0 = L.pl1 = 0.f;
   if (L.player) L.pl0 = s.player_action[i * 2], L.pl1 = s.player_action[i * 2 + 1];  // player-controlled agent (dynamics.py:104-107)
   L.lim_acc = s.max_acc[L.ty], L.lim_yr = s.max_yaw_rate[L.ty];
+  L.act_seed = 0, L.ls0 = L.ls1 = 0.f;
+  if (SAMPLING && (parts & SIM_SAMPLED)) L.act_seed = *s.act_seed, L.ls0 = s.act_log_std[L.ty][0], L.ls1 = s.act_log_std[L.ty][1];
   return L;
 }
 
 // One closed-loop step of agent i by 32 lanes (`sub` = 0..31; half_shift = 0 / 32: which half of the wavefront's ballot is theirs),
 // t = *s.step read by the caller, on loads `Ld` (sim_loads) and the action (am0, am1).
+template <bool SAMPLING = true>
 __device__ __forceinline__ void sim_agent_on(const tbx_sim_state_t& s, const int parts, const int t, const int i, const int sub, const int half_shift,
                                              const SimLoads& Ld, const float am0, const float am1) {
   const int T = s.n_step_out;
@@ -118,10 +138,24 @@ __device__ __forceinline__ void sim_agent_on(const tbx_sim_state_t& s, const int
   const bool append = (parts & TBX_SIM_NO_APPEND) == 0;
   const bool mv0 = append && sub < W - 1;
   // ---------------------------------------------------------------- Dynamics.update_ag + MultiPathPP (dynamics.py:84-120,237-274)
+  // sampled actions (tbx_sim_state_t.act_seed; dynamics.py:87-90): unbounded = mean + std * eps, the sample's log-density. Explicit
+  // fma / add: which products the compiler contracts is otherwise its choice per call site, and every launch form logs the same bits
+  float um0 = am0, um1 = am1, eps0 = 0.f, eps1 = 0.f, act_lp = 0.f;
+  const bool sampled = SAMPLING && (parts & SIM_SAMPLED) != 0;
+  if (sampled) {
+    const tbx_drop::Noise2 e = tbx_drop::action_noise(Ld.act_seed, (uint32_t)t, (uint32_t)i);
+    eps0 = e.e0, eps1 = e.e1;
+    um0 = __fmaf_rn(expf(Ld.ls0), eps0, am0);
+    um1 = __fmaf_rn(expf(Ld.ls1), eps1, am1);
+    const float half_log_2pi = 0.91893853320467274f;
+    const float q0 = __fmaf_rn(0.5f * eps0, eps0, __fadd_rn(Ld.ls0, half_log_2pi));
+    const float q1 = __fmaf_rn(0.5f * eps1, eps1, __fadd_rn(Ld.ls1, half_log_2pi));
+    act_lp = valid0 ? -__fadd_rn(q0, q1) : 0.f;
+  }
   float acc = 0.f, yr = 0.f;
   if (valid0) {
-    acc = tanhf(am0) * lim_acc;
-    yr = tanhf(am1) * lim_yr;
+    acc = tanhf(um0) * lim_acc;
+    yr = tanhf(um1) * lim_yr;
     if (player) acc = Ld.pl0, yr = Ld.pl1;  // player-controlled agent (dynamics.py:104-107)
   }
   const float half_dt = 0.5f * s.dt;
@@ -216,6 +250,11 @@ __device__ __forceinline__ void sim_agent_on(const tbx_sim_state_t& s, const int
     s.out_outside_map[o] = outside ? 1 : 0;
     s.out_dest_reached[o] = reached ? 1 : 0;
     if (s.out_tf != nullptr) s.out_tf[o] = tf_now ? 1 : 0;
+    if (sampled) {
+      s.out_act_noise[o * 2] = eps0;
+      s.out_act_noise[o * 2 + 1] = eps1;
+      s.out_act_log_prob[o] = act_lp;
+    }
     // DifferentiableReward.get on the prediction (rewards.py:58-74; the same expressions as tbx_train_chain_fwd)
     if (s.out_reward != nullptr) {
       float r_pos = 0.f, r_rot = 0.f, r_spd = 0.f;
@@ -258,10 +297,11 @@ __device__ __forceinline__ void sim_agent_on(const tbx_sim_state_t& s, const int
 }
 
 // ... with its own loads and the action from memory (s.action_mean): the stand-alone kernel's form
+template <bool SAMPLING = true>
 __device__ __forceinline__ void sim_agent(const tbx_sim_state_t& s, const int parts, const int t, const int i, const int sub, const int half_shift) {
   const float am0 = s.action_mean[i * 2], am1 = s.action_mean[i * 2 + 1];
-  const SimLoads Ld = sim_loads(s, parts, t, i, sub);
-  sim_agent_on(s, parts, t, i, sub, half_shift, Ld, am0, am1);
+  const SimLoads Ld = sim_loads<SAMPLING>(s, parts, t, i, sub);
+  sim_agent_on<SAMPLING>(s, parts, t, i, sub, half_shift, Ld, am0, am1);
 }
 
 // TBX_SIM_ADVANCE next to a part: every thread of this workgroup has read *step; the last of the n_wg workgroups to arrive advances it

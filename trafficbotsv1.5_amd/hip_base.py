@@ -63,6 +63,27 @@ def drop_mix(counter, lo: int, hi: int):
         return x ^ (x >> np.uint32(16))
 
 
+ACTION_NOISE_SITE = 0x4143544E  # drop_key.h ACTION_NOISE_SITE ("ACTN"): none of the dropout sites' ids
+
+
+def action_noise_bits(seed: int, step: int, scene_row):
+    """drop_key.h action_noise_bits over a numpy array of scene rows -> (h1, h2) uint32 arrays: the integer part of the action noise
+    of (seed, 1-based closed-loop step, row = scene * n_ag + agent of the engine's batch), exact."""
+    lo, hi = drop_stream_key(seed, ACTION_NOISE_SITE, step)
+    with np.errstate(over="ignore"):
+        r = np.asarray(scene_row).astype(np.uint32) * np.uint32(2)
+        return drop_mix(r, lo, hi), drop_mix(r + np.uint32(1), lo, hi)
+
+
+def action_noise(seed: int, step: int, scene_row):
+    """drop_key.h action_noise in float64 -> [len(scene_row), 2]: Box-Muller on u1 = (h1 + 1) * 2^-32 in (0, 1], theta = 2 pi h2 * 2^-32.
+    What tbx_sim_step logs into out_act_noise agrees with this to 1e-5."""
+    h1, h2 = action_noise_bits(seed, step, scene_row)
+    r = np.sqrt(-2.0 * np.log((h1.astype(np.float64) + 1.0) * 2.0 ** -32))
+    th = 2.0 * np.pi * (h2.astype(np.float64) * 2.0 ** -32)
+    return np.stack([r * np.cos(th), r * np.sin(th)], -1)
+
+
 def _fill_drop(a, drop: dict) -> None:
     """The drop_* fields of a tile struct from drop = dict(p, seed int64[1] device tensor, step, sites = site ids, None: not dropped)."""
     a.drop_thresh, a.drop_scale = drop_rate(drop["p"])

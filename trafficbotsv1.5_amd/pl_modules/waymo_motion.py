@@ -131,9 +131,11 @@ class WaymoMotion(LightningModule):
     # ------------------------------------------------------------------ rollout
     def begin_rollout(self, ag_tokens: Dict[str, Tensor], mp_tokens: Dict[str, Tensor], tl_tokens: Dict[str, Tensor],
                       tl_state_gt: Tensor, teacher_forcing: TeacherForcing, rule_checker: TrafficRuleChecker, step_end: int,
-                      stepwise: bool = False) -> RolloutEngine:
+                      stepwise: bool = False, deterministic_action: bool = True) -> RolloutEngine:
         """Step 0 of `rollout` (waymo_motion.py:218-231: teacher_forcing.init, dynamics.init, model.init): the device-resident
-        simulation state. stepwise: driven through `forward` instead of the engine's own loop."""
+        simulation state. stepwise: driven through `forward` instead of the engine's own loop. deterministic_action=False: every step
+        samples its actions (Dynamics.update_ag's rsample, dynamics.py:87-90) from a seed the engine draws from torch's generator of the
+        device here - `torch.manual_seed(s)` before the call reproduces the rollout."""
         teacher_forcing.init(ag_valid=ag_tokens["gt_valid"], ag_pose=ag_tokens["gt_pose"], ag_motion=ag_tokens["gt_motion"],
                              tl_state=tl_state_gt, current_epoch=self.current_epoch)
         dev = ag_tokens["gt_pose"].device
@@ -146,24 +148,24 @@ class WaymoMotion(LightningModule):
                   map_pos=rule_checker.mp_pos, map_dir=rule_checker.mp_dir, map_boundary=rule_checker.mp_boundary,
                   n_step=step_end, reward_weights=(rc.l_pos.weight, rc.l_rot.weight, rc.l_spd.weight),
                   ag_navi_log_prob=ag_tokens.get("ag_navi_log_prob"), stepwise=stepwise)
-        eng = self._engine_for(kw, dev)
+        eng = self._engine_for(kw, dev, sample_actions=not deterministic_action)
         self.dynamics.bind(eng)
         return eng
 
-    def _engine_for(self, kw: dict, dev) -> RolloutEngine:
-        """One engine per (shapes, schedule, weights), refilled in place: a loop over scenes (validation_step, waymo_motion.py:526)
+    def _engine_for(self, kw: dict, dev, sample_actions: bool = False) -> RolloutEngine:
+        """One engine per (shapes, schedule, sampled / deterministic actions, weights), refilled in place: a loop over scenes (validation_step, waymo_motion.py:526)
         captures its hipGraphs once. `engine_cache = 0` turns the cache off (a fresh engine per rollout). kw: RolloutEngine.reset's."""
         mp_tokens, tl_tokens = kw["mp_tokens"], kw["tl_tokens"]
         sched = self.schedule if self.schedule is not None else engine.current()
         # (weights: every parameter's storage AND version - an optimizer step, load_state_dict, .to() or `p.data = ` all change one)
-        key = (RolloutEngine.shape_key(**kw), dataclasses.astuple(sched), str(dev), self.training,
+        key = (RolloutEngine.shape_key(**kw), dataclasses.astuple(sched), str(dev), self.training, bool(sample_actions),
                hash(weights_stamp(self.model.parameters())))
         eng = self._engines.get(key) if self.engine_cache > 0 else None
         if eng is not None:
             eng.refill(**kw)
             self._engines.move_to_end(key)
         else:
-            eng = RolloutEngine(self.model, self.dynamics, dev, schedule=sched)
+            eng = RolloutEngine(self.model, self.dynamics, dev, schedule=sched, sample_actions=sample_actions)
             if self.engine_cache > 0:
                 # a cached engine is refilled in place with later scenes: it owns COPIES of the first scene's token dicts (one copy
                 # per engine, not per rollout), so a caller still holding encode_scene()'s output never sees it change
@@ -182,16 +184,17 @@ class WaymoMotion(LightningModule):
     def rollout(self, ag_tokens: Dict[str, Tensor], mp_tokens: Dict[str, Tensor], tl_tokens: Dict[str, Tensor],
                 tl_state_gt: Tensor, teacher_forcing: TeacherForcing, rule_checker: TrafficRuleChecker, step_end: int,
                 deterministic_action: bool, player_policy=None, use_graph: bool = True, stepwise: bool = False) -> RolloutBuffer:
-        """Reference signature (waymo_motion.py:206-217). Inference only: deterministic actions, no autograd.
+        """Reference signature (waymo_motion.py:206-217). Inference only: no autograd. deterministic_action=False samples every step's
+        action inside tbx_sim_step (same launches, same graph replays; the buffer's action_log_prob is the samples', vis_dict
+        "action_noise" the eps drawn); `torch.manual_seed` before the call reproduces it.
         Default: the engine's device-side loop (one hipGraph replay per step). With a `player_policy` - a callable
         `ag_pose [n_sc, n_ag, 3] -> None | {"valid": [n_sc, n_ag] bool, "action": [n_sc, n_ag, 2]}` asked before every step,
         the hook the reference leaves as a todo (:240-241) - or stepwise=True, the reference's Python loop itself, one `forward`
         per step; both produce the same buffer (tested bit for bit)."""
-        if not deterministic_action:
-            raise NotImplementedError("stochastic actions are not used by any default entry point")
         stepwise = stepwise or player_policy is not None
         if not stepwise:
-            eng = self.begin_rollout(ag_tokens, mp_tokens, tl_tokens, tl_state_gt, teacher_forcing, rule_checker, step_end)
+            eng = self.begin_rollout(ag_tokens, mp_tokens, tl_tokens, tl_state_gt, teacher_forcing, rule_checker, step_end,
+                                     deterministic_action=deterministic_action)
             eng.run(step_end, use_graph=use_graph)
             return eng.buffer(self.hp.time_step_current, rule_checker=rule_checker)
         # ---- the reference's loop, statement by statement (waymo_motion.py:218-311)
@@ -236,17 +239,21 @@ class WaymoMotion(LightningModule):
         Dynamics.update_ag (player_override: {"valid", "action"} replaces the policy's physical action), then
         Dynamics.override_ag(ag_override {"valid", "pose", "motion"}) and override_tl(tl_override {"valid", "state"}).
         Returns (pred_dict, vis_dict) with the reference's keys. Rule checks and disable_ag / disable_navi stay with the caller
-        (`self.dynamics.disable_ag(violation, gt_valid)`), as in the reference's `rollout`."""
+        (`self.dynamics.disable_ag(violation, gt_valid)`), as in the reference's `rollout`.
+        deterministic_action=False: the step's action is sampled (pred_dict "action_log_prob" is the sample's, vis_dict "action_noise"
+        the eps drawn). Sampled or not is a property of the rollout's engine - begin_rollout's argument, or this argument at the first
+        `forward` after Dynamics.init - and every `forward` of the rollout must say the same."""
         if self.dynamics._pending is not None:
-            eng = self._engine_from_init(mp_tokens, tl_tokens)
+            eng = self._engine_from_init(mp_tokens, tl_tokens, sample_actions=not deterministic_action)
         else:
             eng = self._engine
         if eng is None or not eng.stepwise or self.dynamics._eng is not eng:
             raise RuntimeError("forward() steps the simulation state that the reference's rollout prologue sets up - teacher_forcing.init, "
                                "self.dynamics.init(tl_state=..., **ag_tokens), self.model.init() (waymo_motion.py:218-229) - or "
                                "begin_rollout(..., stepwise=True)")
-        if not deterministic_action:
-            raise NotImplementedError("stochastic actions are not used by any default entry point")
+        if eng.sample_actions != (not deterministic_action):
+            raise ValueError(f"forward(deterministic_action={deterministic_action}): this rollout's engine was built with "
+                             f"deterministic_action={not eng.sample_actions} (begin_rollout / the first forward); start another rollout to change it")
         if eng._n_forward >= eng.T:
             raise RuntimeError(f"forward(): the engine logs {eng.T} steps per rollout (hparams.time_step_end, or rollout's step_end); "
                                "call self.dynamics.init(...) again to start another rollout")
@@ -256,7 +263,7 @@ class WaymoMotion(LightningModule):
             slot = eng.forward_step(ag_override, tl_override, player_override)
         S, n, L = eng.S, eng.n, eng.L
         pred_valid = S["out_valid"][:, :, slot].bool()
-        pred_dict = {"action_log_prob": eng.action_log_prob(S["out_valid"][:, :, slot]), "pred_valid": pred_valid,
+        pred_dict = {"action_log_prob": eng.action_log_prob(S["out_valid"][:, :, slot], slot=slot), "pred_valid": pred_valid,
                      "pred_pose": S["out_pose"][:, :, slot], "pred_motion": S["out_motion"][:, :, slot],
                      "pred_tl_state_dist": torch.distributions.Categorical(logits=S["tl_logits"].view(n, L, -1).clone())}
         vis_dict = {}
@@ -265,9 +272,11 @@ class WaymoMotion(LightningModule):
             vis_dict = {"pred_valid": dyn.ag_valid, "pred_pose": dyn.ag_pose.clone(), "pred_motion": dyn.ag_motion.clone(),
                         "action": S["out_action"][:, :, slot], "ag_navi": dyn.ag_navi, "ag_navi_valid": dyn.ag_navi_valid,
                         "navi_reached": dyn.mask_navi_reached, "tl_state": dyn.tl_state}
+            if eng.sample_actions:
+                vis_dict["action_noise"] = S["out_act_noise"][:, :, slot]
         return pred_dict, vis_dict
 
-    def _engine_from_init(self, mp_tokens: Dict[str, Tensor], tl_tokens: Dict[str, Tensor]) -> RolloutEngine:
+    def _engine_from_init(self, mp_tokens: Dict[str, Tensor], tl_tokens: Dict[str, Tensor], sample_actions: bool = False) -> RolloutEngine:
         """The step-wise engine of a rollout that was started the reference's way (Dynamics.init + TrafficBots.init), built by the
         first `forward` - the call that brings the tokens. Its tbx_sim_step copies of the outside-map / destination checks get
         tables that never fire: the caller's `rule_checker.check` evaluates them and `dynamics.disable_ag / disable_navi` apply them."""
@@ -277,7 +286,7 @@ class WaymoMotion(LightningModule):
         kw = dict(tf_mask=torch.zeros_like(p["gt_valid"]), mp_tokens=mp_tokens, tl_tokens=tl_tokens, map_valid=None, map_type=None, map_pos=None,
                   map_dir=None, map_boundary=None, n_step=int(getattr(self, "_forward_steps", None) or self.hparams.time_step_end),
                   reward_weights=(rc.l_pos.weight, rc.l_rot.weight, rc.l_spd.weight), stepwise=True, **p)
-        eng = self._engine_for(kw, dev)
+        eng = self._engine_for(kw, dev, sample_actions=sample_actions)
         self.dynamics.bind(eng)
         self._forward_steps = None
         return eng
@@ -308,8 +317,10 @@ class WaymoMotion(LightningModule):
     @torch.no_grad()
     def joint_future_pred(self, batch, mp_tokens, tl_tokens, ag_latent_dist: Optional[MyDist], ag_navi_dist: Optional[MyDist],
                           teacher_forcing: TeacherForcing, n_joint_future: int, step_end: Optional[int] = None,
-                          use_graph: bool = True) -> RolloutBuffer:
-        """waymo_motion.py:439-524: K parallel rollouts per scene from the history only. mp_tokens / tl_tokens exactly as
+                          use_graph: bool = True, deterministic_action: bool = True) -> RolloutBuffer:
+        """waymo_motion.py:439-524: K parallel rollouts per scene from the history only. deterministic_action (the reference passes
+        True to `rollout` here, :520): False also samples every step's action - futures with identical latents and destinations then
+        still differ. mp_tokens / tl_tokens exactly as
         `model.mp_encoder(...)` and `model.tl_encoder.pre_compute(tl_valid=..., **mp_tokens)` return them (validation_step,
         :528-535): the per-rollout repeat of the reference (:458-462) happens here, on a COPY of the light tokens (the caller's dicts
         stay as they are - `reactive_replay` has read the same ones), and only for the lights: the K rollouts of a scene share one copy
@@ -339,7 +350,7 @@ class WaymoMotion(LightningModule):
         ag_tokens["ag_navi_log_prob"] = ag_navi_dist.log_prob(ag_tokens["ag_navi"]).masked_fill(~ag_tokens["ag_navi_valid"], 0)
         checker = self._rule_checker(batch, ag_tokens["ag_navi"], tl_tokens, n_rollout=K)
         buf = self.rollout(ag_tokens, mp_tokens, tl_tokens, r(batch["sc/tl_state"]), teacher_forcing, checker,
-                           step_end or self.hp.time_step_end, True, use_graph=use_graph)
+                           step_end or self.hp.time_step_end, deterministic_action, use_graph=use_graph)
         buf.flatten_joint_future(K)
         buf.compute_log_prob(ag_latent_log_prob)
         return buf

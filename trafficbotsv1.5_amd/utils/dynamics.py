@@ -1,7 +1,12 @@
 """`Dynamics` / `MultiPathPP` (utils/dynamics.py:13-274). The state update itself (tanh-bounded action -> MultiPath++ midpoint
 integration -> overrides -> disabling) is `tbx_sim_step`; the state lives in the rollout engine's device buffers. For step-wise
 drivers (`WaymoMotion.forward`) this object exposes that state under the reference's attribute names and the two methods the
-reference's `rollout` calls between two `forward`s (disable_ag / disable_navi)."""
+reference's `rollout` calls between two `forward`s (disable_ag / disable_navi).
+
+`update_ag(action_dist, deterministic, player_override)` of the reference has no counterpart method: the policy's mean never leaves the
+device, and with deterministic=False `tbx_sim_step` itself draws the sample (mean + exp(log_std) * eps, eps keyed by the engine's
+seed, the step counter and the agent's row) and logs eps and the sample's log-probability. `sample_actions` says which of the two
+the bound rollout does; `WaymoMotion.forward(deterministic_action=...)` must agree with it."""
 from typing import Dict, Optional, Tuple
 
 from torch import Tensor
@@ -69,6 +74,7 @@ class Dynamics:
                                "(WaymoMotion.rollout(..., stepwise=True) / begin_rollout(..., stepwise=True))")
         return self._eng.S[key]
 
+    sample_actions = property(lambda self: bool(self._eng is not None and self._eng.sample_actions))
     ag_valid = property(lambda self: self._s("ag_valid").bool())
     ag_disabled = property(lambda self: self._s("ag_disabled").bool())
     ag_pose = property(lambda self: self._s("ag_pose"))

@@ -76,9 +76,13 @@ class RolloutEngine:
             cls._streams[key] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
         return cls._streams[key]
 
-    def __init__(self, model, dynamics, device, schedule: Optional[engine.Schedule] = None) -> None:
+    def __init__(self, model, dynamics, device, schedule: Optional[engine.Schedule] = None, sample_actions: bool = False) -> None:
+        """sample_actions: Dynamics.update_ag with deterministic=False (dynamics.py:87-90) - every step adds exp(log_std) * eps to the
+        action mean inside tbx_sim_step (tbx_sim_state_t.act_seed) and logs eps and the sample's log-probability. Fixed at
+        construction like the schedule: the captured graphs hold the descriptor that says so."""
         self.model, self.dyn, self.dev = model, dynamics, device
         self.sched = schedule if schedule is not None else engine.current()
+        self.sample_actions = bool(sample_actions)
         self._graph_steps = 1  # steps per replay of graph_multi, fixed when it is captured
         self.reused = False    # True: kept by its owner across rollouts (refill): buffer() hands out copies of the logs
         self.graph: Optional[torch.cuda.CUDAGraph] = None
@@ -91,7 +95,7 @@ class RolloutEngine:
               ag_navi_valid: Tensor, mp_tokens: Dict[str, Tensor], tl_tokens: Dict[str, Tensor], map_valid: Optional[Tensor],
               map_type: Optional[Tensor], map_pos: Optional[Tensor], map_dir: Optional[Tensor], map_boundary: Optional[Tensor], n_step: int,
               reward_weights=(0.1, 10.0, 0.1), ag_navi_log_prob: Optional[Tensor] = None, stepwise: bool = False,
-              _lights_ahead_pass: bool = True, _tl_div: Optional[int] = None) -> None:
+              _lights_ahead_pass: bool = True, _tl_div: Optional[int] = None, _act_log_std=None) -> None:
         """All tensors on the device. gt_* [n,A,Tg(,3)], tl_state_gt [n,L,Tt,5] bool, tf_mask [n,A,Tg] bool
         (TeacherForcing.ag_teacher_forcing), ag_navi [n,A] int64 dest; map_* are the raw polylines of the scene(s)
         ([n/div, M, N, ..]) for the destination check. reward_weights = (l_pos, l_rot, l_spd).weight of the
@@ -187,6 +191,15 @@ class RolloutEngine:
                  # the rest of RolloutBuffer.add (buffer.py:39-78): reward terms, its validity, the forcing mask, light NLL
                  out_reward=z(n, A, n_step, 4), out_reward_valid=z(n, A, n_step, dt=u8), out_tf=z(n, A, n_step, dt=u8),
                  out_tl_nll=z(nl, L, n_step))
+        if self.sample_actions:
+            # ONE uint64 seed word per engine, drawn on the device from torch's generator of this device (torch.manual_seed reproduces
+            # a rollout; graph-safe, so a captured refill draws a new one at every replay) and never read back: tbx_sim_step reads it
+            # through the pointer at every step, a refill's commit copies the new scene's draw into the same word
+            S["act_seed"] = torch.empty(1, dtype=torch.int64, device=dev).random_()
+            S.update(out_act_noise=z(n, A, n_step, 2), out_act_log_prob=z(n, A, n_step))
+            # (the head's log_std on the host: read once per engine - a refill's scratch engine, possibly under capture, is handed it)
+            self._act_log_std = _act_log_std if _act_log_std is not None else [[float(v) for v in p.detach().cpu().tolist()]
+                                                                               for p in self.model.action_head.log_std]
         if stepwise:  # WaymoMotion.forward: this step's overrides, the player's actions, the this-step rule flags
             S.update(ov_valid=z(n, A, dt=u8), ov_pose=z(n, A, 3), ov_motion=z(n, A, 3), ov_tl_valid=z(nl, L, dt=u8),
                      ov_tl_state=z(nl, L, dt=u8), now_outside=z(n, A, dt=u8), now_reached=z(n, A, dt=u8),
@@ -203,6 +216,10 @@ class RolloutEngine:
         st.max_yaw_rate = (C.c_float * 3)(*self.dyn.max_yaw_rate)
         st.dt = self.dyn.dt
         st.w_pos, st.w_rot, st.w_spd = (float(w) for w in reward_weights)
+        if self.sample_actions:
+            for ty in range(3):
+                for d in range(2):
+                    st.act_log_std[ty][d] = self._act_log_std[ty][d]
         self.sim_state = st
         # the lights' part of tbx_sim_step only touches the light arrays: its own descriptor with their batch size
         self.sim_state_tl = st
@@ -258,8 +275,8 @@ class RolloutEngine:
         key = self.shape_key(**kw)
         if key != self._shape_key:
             raise ValueError("refill: shapes differ from the ones this engine was built for (use a new engine)")
-        fresh = RolloutEngine(self.model, self.dyn, self.dev, schedule=self.sched)
-        RolloutEngine.reset.__wrapped__(fresh, _lights_ahead_pass=False, _tl_div=self.tl_div, **kw)
+        fresh = RolloutEngine(self.model, self.dyn, self.dev, schedule=self.sched, sample_actions=self.sample_actions)
+        RolloutEngine.reset.__wrapped__(fresh, _lights_ahead_pass=False, _tl_div=self.tl_div, _act_log_std=getattr(self, "_act_log_std", None), **kw)
         return fresh
 
     @_scheduled
@@ -660,7 +677,15 @@ class RolloutEngine:
             S["navi_valid"] &= 1 - reached.to(torch.uint8)
 
     # ------------------------------------------------------------------ results
-    def action_log_prob(self, valid_u8: Tensor) -> Tensor:
+    def action_log_prob(self, valid_u8: Tensor, slot: Optional[int] = None) -> Tensor:
+        """Dynamics.update_ag's action_log_prob. Sampled actions: what tbx_sim_step logged for the sample (out_act_log_prob; slot: one
+        step of it, else the whole log). Deterministic actions: the closed form below."""
+        if self.sample_actions:
+            lp = self.S["out_act_log_prob"]
+            return lp.clone() if slot is None else lp[:, :, slot].clone()
+        return self._mean_log_prob(valid_u8)
+
+    def _mean_log_prob(self, valid_u8: Tensor) -> Tensor:
         """Dynamics.update_ag's action_log_prob with deterministic actions (dynamics.py:87-91): log N(mean | mean, std) of the
         2-d action = -sum_d (log_std_d + log sqrt(2 pi)) per agent type, 0 for invalid agents. valid_u8 [n, A, ...]."""
         ls = torch.stack(list(self.model.action_head.log_std), 0).sum(-1)  # [3]
@@ -698,6 +723,8 @@ class RolloutEngine:
             buf.violation.update(rule_checker.check_log(S["out_valid"], S["out_pose"], S["out_motion"], out_tl))
         bits = (out_tl.to(torch.int32).unsqueeze(-1) >> torch.arange(5, device=self.dev, dtype=torch.int32)) & 1
         buf.vis_dict = {"action": S["out_action"], "tl_state": bits.bool()}
+        if self.sample_actions:
+            buf.vis_dict["action_noise"] = S["out_act_noise"]  # the eps every sampled action was drawn with
         # what the reference's loop adds per step besides the prediction (waymo_motion.py:250-300)
         r = S["out_reward"]
         buf.diffbar_reward = {"diffbar_reward_valid": b8(S["out_reward_valid"]), "diffbar_reward": r[..., 3],
