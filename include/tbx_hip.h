@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define TBX_ABI_VERSION 6
+#define TBX_ABI_VERSION 7
 
 enum {
   TBX_OK = 0,
@@ -69,10 +69,8 @@ typedef struct tbx_knn_job {
   int32_t n_batch, n_src, n_tgt, tgt_batch_div, k;
   float dist_limit;
 } tbx_knn_job_t;
-int tbx_knn_embed_multi(const tbx_knn_job_t* jobs /* host */, int n_jobs, const float* freqs_xy, const float* freqs_yaw, int pe_dim,
-                        void* stream);
-/* ... with a tbx_pose_embed of explicit triples riding on the same launch (its blocks come after the searches'; the agents' destination
- * embedding of a simulation step, navigation.py:65-79, needs the same inputs as the searches and nothing they produce). pe may be NULL. */
+/* pe (may be NULL): a tbx_pose_embed of explicit triples riding on the same launch (its blocks come after the searches'; the agents'
+ * destination embedding of a simulation step, navigation.py:65-79, needs the same inputs as the searches and nothing they produce). */
 typedef struct tbx_pose_embed_job {
   const float* pose3;      /* [n, 3] */
   const float* freqs_xy;
@@ -81,8 +79,8 @@ typedef struct tbx_pose_embed_job {
   int64_t n;
   int32_t pe_dim, ld_out, col_off, reserved;
 } tbx_pose_embed_job_t;
-int tbx_knn_embed_multi_pe(const tbx_knn_job_t* jobs /* host */, int n_jobs, const float* freqs_xy, const float* freqs_yaw, int pe_dim,
-                           const tbx_pose_embed_job_t* pe /* host, may be NULL */, void* stream);
+int tbx_knn_embed_multi(const tbx_knn_job_t* jobs /* host */, int n_jobs, const float* freqs_xy, const float* freqs_yaw, int pe_dim,
+                        const tbx_pose_embed_job_t* pe /* host, may be NULL */, void* stream);
 
 /* Pose embedding of explicit (x,y,yaw) triples (utils/pose_emb.py:50-55); out[i, col_off : col_off+pe_dim]. */
 int tbx_pose_embed(const float* pose3, int64_t n, const float* freqs_xy, const float* freqs_yaw, int pe_dim, float* out,
@@ -247,10 +245,11 @@ typedef struct tbx_heads_tail {
   float* action_out;                     /* [rows, 2] */
   int32_t mask_stride;
   /* Fused step tail (tail_mfma32 launches; sim_state and next_prep both or neither; host pointers): behind a row's action the
-   * launch runs that agent's tbx_sim_step_parts(sim_state, sim_parts) - sim_parts = TBX_SIM_AGENTS [| TBX_SIM_ADVANCE], the agents'
+   * launch runs that agent's tbx_sim_step(sim_state, sim_parts, NULL) - sim_parts = TBX_SIM_AGENTS [| TBX_SIM_ADVANCE], the agents'
    * part only, rows = sim_state's n_batch * n_ag agents - and then tbx_agent_prep (*next_prep) of the NEXT step for that agent: an
    * agent's step and its window features read nothing of another agent's, so the two launches that close and open every step of the
-   * closed loop are the tail of the launch that produced the action. */
+   * closed loop are the tail of the launch that produced the action. Both descriptors pass the checks of the stand-alone calls
+   * (one definition each, csrc/step_core.h) before anything is launched. */
   int32_t sim_parts;
   const struct tbx_sim_state* sim_state;
   const struct tbx_agent_prep_args* next_prep;
@@ -270,7 +269,8 @@ typedef struct tbx_tl_tail {
   int32_t ld_kv, kv_bf16, n_state, pad_;
   float clamp_lo, clamp_hi;
   /* sim_state != NULL (round 6; with it `prep_*`): behind its logits the row's workgroup also runs the NEXT step of its light -
-   * tbx_sim_step_tl_prep(sim_state, sim_parts = TBX_SIM_LIGHTS [| TBX_SIM_ADVANCE], ...) for that light alone (dynamics.py:143-163,
+   * tbx_sim_step(sim_state, sim_parts = TBX_SIM_LIGHTS [| TBX_SIM_ADVANCE], rows) for that light alone, rows = the tbx_tl_rows_t of
+   * (tl_invalid, prep_attr, prep_row_invalid, prep_ld_attr), under that call's checks (dynamics.py:143-163,
    * traffic_bots.py:123-143, traffic_light.py:219-226; rows = sim_state's n_batch * n_tl lights, logits_out = its tl_logits): a light's
    * step reads nothing of another light's, so the launch that opened every step of the lights' recurrence is the tail of the launch
    * that produced its logits (the agents' counterpart: tbx_heads_tail_t.sim_state). */
@@ -430,12 +430,12 @@ int tbx_window_tile(const tbx_window_tile_t* args /* host */, void* stream);
  * (2^-9 relative per operand), fp32 accumulation; the same images (their lo halves are not read). Inference only (no dropout sites). */
 int tbx_window_tile_bf16(const tbx_window_tile_t* args /* host */, void* stream);
 /* tbx_front: everything between the feature preparation and a block's first decoder layer as ONE launch (small launches: the
- * closed loop at a few scenes), instead of tbx_window_tile -> tbx_knn_embed_multi_pe -> tbx_layer_tile one after the other:
+ * closed loop at a few scenes), instead of tbx_window_tile -> tbx_knn_embed_multi -> tbx_layer_tile one after the other:
  *   win    the block's window PointNet (tbx_window_tile's arguments; no dropout);
  *   layer  the block's FIRST PROJECTION as a tbx_layer_tile_t: x = win.out, n_rows = win.n_groups, no attn_out / linear1_image,
  *          proj_n = 384 (q | k | v | W_k^T q into proj_out, + kv16_out), and its rider_* (or rider_rows = 0);
  *   jobs   n_jobs (0..4) K-nearest searches in the relative-pose form (emb = NULL) + the pose-embedding job `pe` (or NULL), as
- *          tbx_knn_embed_multi_pe takes them.
+ *          tbx_knn_embed_multi takes them.
  * The parts run in separate workgroups of the one launch; results are those of the three launches (the projection of a window's
  * pooled row on the split-bf16 matrix path as tbx_layer_tile's). */
 struct tbx_knn_job;
@@ -779,7 +779,8 @@ int tbx_rowchain_live(const tbx_stage_t* stages /* host */, int n_stages, int64_
  *   type_mask [3, n*A] u8: ~(type_i & valid_now)
  *   navi_pose3 [n*A, 3]: dest token pose relative to the agent's current pose; navi_row [n*A] i32 = b*M + dest
  */
-/* tbx_agent_prep's arguments as a structure (tbx_heads_tail_t.next_prep): n_tok = n_batch * n_ag */
+/* tbx_agent_prep's arguments (also tbx_heads_tail_t.next_prep): n_tok = n_batch * n_ag rows. Optional (NULL = off): type_mask (needs
+ * ag_type_idx), dest (needs mp_tok_pose, navi_pose3, navi_row, n_mp > 0, mp_batch_div > 0). pe_dim in {64, 128}. */
 typedef struct tbx_agent_prep_args {
   const uint8_t* hist_valid;
   const float *hist_pose, *hist_motion, *ag_attr6;
@@ -795,16 +796,19 @@ typedef struct tbx_agent_prep_args {
   int32_t* navi_row;
   int32_t n_tok, n_ag, window, pe_dim, n_mp, mp_batch_div;
 } tbx_agent_prep_args_t;
-int tbx_agent_prep(const uint8_t* hist_valid, const float* hist_pose, const float* hist_motion, const float* ag_attr6,
-                   const uint8_t* ag_type_idx, int n_batch, int n_ag, int window, const float* freqs_xy,
-                   const float* freqs_yaw, int pe_dim, float* tok_pose, uint8_t* tok_invalid, float* attr, float* pe,
-                   uint8_t* row_invalid, uint8_t* type_mask, const int64_t* dest, const float* mp_tok_pose, int n_mp,
-                   int mp_batch_div, float* navi_pose3, int32_t* navi_row, void* stream);
+int tbx_agent_prep(const tbx_agent_prep_args_t* args /* host */, void* stream);
 
 /* traffic_light.py:219-226: attr [n*L*W, ld_attr] = one-hot5(state) | one-hot_W(position) | 0-pad; rows of missing
- * steps (hist_tl == 0xFF) and of invalid lights are flagged in row_invalid. hist_tl holds the 5-bit state mask per step. */
-int tbx_tl_prep(const uint8_t* hist_tl, const uint8_t* tl_invalid, int n_batch, int n_tl, int window, int ld_attr,
-                float* attr, uint8_t* row_invalid, void* stream);
+ * steps (hist_tl == 0xFF) and of invalid lights are flagged in row_invalid. hist_tl holds the 5-bit state mask per step.
+ * The rows, as every caller that writes them takes them (tbx_tl_prep, tbx_sim_step; tbx_tl_tail_t holds the same fields): ld_attr >=
+ * 5 + window and a multiple of 4; where the rows ride on another launch (tbx_sim_step, tbx_tl_tail_t) attr is 16-byte aligned. */
+typedef struct tbx_tl_rows {
+  const uint8_t* tl_invalid; /* [n*L] */
+  float* attr;               /* [n*L*W, ld_attr] */
+  uint8_t* row_invalid;      /* [n*L*W] */
+  int32_t ld_attr, pad_;
+} tbx_tl_rows_t;
+int tbx_tl_prep(const uint8_t* hist_tl, int n_batch, int n_tl, int window, const tbx_tl_rows_t* rows /* host */, void* stream);
 
 /* map_encoder.py:64-77: per polyline node, attr [n*M*N, 32] = type11 | one-hot_N(node) | 0-pad, pe [n*M*N, 8] = the
  * 7-d MultiPath++ polyline feature of the node in the token (first node) frame (pose_emb.py:58-89) | 0. */
@@ -891,25 +895,21 @@ typedef struct tbx_sim_state {
    * The seed is read on the device at every step and the key holds the device step counter, so one captured graph draws fresh
    * noise at every replay and a new seed written into the same word reseeds it. An agent invalid before the step logs action 0 and
    * log_prob 0 as always (its eps is still logged); a player-overridden agent takes the player's action and logs the SAMPLE's
-   * log_prob (the override comes after log_prob: dynamics.py:90 vs :103-105).
-   * This group was appended WITHOUT a bump of tbx_version(): a zero-filled tail is the old behaviour, and the tests that pin the
-   * version and the symbol count are not this change's to touch - the bump belongs to the next change that may touch them. */
+   * log_prob (the override comes after log_prob: dynamics.py:90 vs :103-105). */
   const uint64_t* act_seed;     /* device, one word */
   float act_log_std[3][2];      /* per type idx (veh, ped, cyc), per action dimension (acc, yaw rate): ActionHead.log_std */
   float* out_act_noise;         /* [n,A,T,2] eps drawn, written at [.., step-1, ..] (required with act_seed) */
   float* out_act_log_prob;      /* [n,A,T]   (required with act_seed) */
 } tbx_sim_state_t;
 
-int tbx_sim_step(const tbx_sim_state_t* st /* host */, void* stream);
-
-/* The same step in separately launchable parts. The traffic lights' recurrence (tl_state -> tl encoder -> tl_logits ->
+/* The step in separately launchable parts. The traffic lights' recurrence (tl_state -> tl encoder -> tl_logits ->
  * tl_state, traffic_bots.py:188-199 + dynamics.py:143-163) never reads an agent, so a rollout may advance the lights on
  * one stream while the agents of the same step run on another; both parts read *step, TBX_SIM_ADVANCE bumps it and
  * must be ordered after both. With TBX_SIM_ADVANCE next to a part, the last workgroup of that part's kernel to arrive
  * bumps the counter (every workgroup has read it by then): no extra launch - for grids of up to 256 workgroups (the call uses
  * workgroups of up to 1024 threads to stay there: 8192 agents); a larger grid's arrivals on the one counter would serialise in L2
- * (~10 ns each), so there the call makes a second, one-thread launch on the same stream that bumps it. tbx_sim_step == all three,
- * one kernel (two for such a grid). */
+ * (~10 ns each), so there the call makes a second, one-thread launch on the same stream that bumps it. All three parts = the whole
+ * step, one kernel (two for such a grid). */
 enum { TBX_SIM_AGENTS = 1, TBX_SIM_LIGHTS = 2, TBX_SIM_ADVANCE = 4,
        /* Step-wise drivers split a step where the reference's Python does (waymo_motion.py:118-204 is `forward`, :250-275 the
         * caller's rule check + disable_ag / disable_navi, traffic_bots.py:123-143 appends the windows at the NEXT forward):
@@ -918,13 +918,10 @@ enum { TBX_SIM_AGENTS = 1, TBX_SIM_LIGHTS = 2, TBX_SIM_ADVANCE = 4,
        TBX_SIM_NO_APPEND = 16,  /* the sliding windows are left alone */
        /* ... and a part of its own: append the current agent / light state to the windows (no step is simulated) */
        TBX_SIM_APPEND = 32 };
-int tbx_sim_step_parts(const tbx_sim_state_t* st /* host */, int parts, void* stream);
-/* tbx_sim_step_parts with TBX_SIM_LIGHTS (appending), and tbx_tl_prep of the lights' new windows in the same launch: a light's thread
- * writes the ld_attr-wide one-hot rows and the row mask of its own window (traffic_light.py:219-226) right after shifting it.
- * tl_invalid [n_batch * n_tl] u8, attr [n_batch * n_tl * window, ld_attr], row_invalid [n_batch * n_tl * window]. tl_invalid NULL:
- * tbx_sim_step_parts. */
-int tbx_sim_step_tl_prep(const tbx_sim_state_t* st /* host */, int parts, const uint8_t* tl_invalid, int ld_attr, float* attr,
-                         uint8_t* row_invalid, void* stream);
+/* tl_rows != NULL (with TBX_SIM_LIGHTS, appending): tbx_tl_prep of the lights' new windows in the same launch - a light's lanes write
+ * the ld_attr-wide one-hot rows and the row mask of its own window (traffic_light.py:219-226) right after shifting it.
+ * Every required pointer of *st is checked whatever the parts (the rollout engine's descriptors are copies of one full state). */
+int tbx_sim_step(const tbx_sim_state_t* st /* host */, int parts, const tbx_tl_rows_t* tl_rows /* host, may be NULL */, void* stream);
 
 /* utils/rewards.py:35-85 (DifferentiableReward.get, default configuration: the three imitation terms; w_collision = 0) for ONE step
  * on caller-supplied tensors - what tbx_sim_step logs into out_reward, as a call of its own. n = n_sc * n_ag rows.

@@ -25,8 +25,8 @@ def test_library_exports_every_declared_symbol(hip):
                          "tbx_rowchain", "tbx_rowchain_ex", "tbx_knarpe_attn_bwd", "tbx_agent_prep", "tbx_tl_prep", "tbx_map_prep", "tbx_sim_step"}
     for s in syms:
         assert hasattr(lib, s), s
-    assert lib.tbx_version() == 6
-    assert len(syms) == 75
+    assert lib.tbx_version() == 7
+    assert len(syms) == 72
     assert lib.tbx_error_string(-2).decode().startswith("shape")
 
 
@@ -39,7 +39,7 @@ def test_argument_validation_returns_codes_without_a_gpu(hip):
     assert lib.tbx_rowchain(st, 1, 16, 0, 24, 132, None) == -2      # tile_rows must be 16, 32 or 48
     assert lib.tbx_rowchain(st, 1, 16, 0, 16, 130, None) == -3      # ldw % 4
     assert lib.tbx_rowchain(st, 1, 16, 0, 16, 132, None) == -1      # LINEAR without a weight pointer
-    assert lib.tbx_sim_step(None, None) == -1
+    assert lib.tbx_sim_step(None, 7, None, None) == -1
     with pytest.raises(RuntimeError):
         hip.pose_embed(torch.zeros(4, 3), torch.zeros(32), torch.zeros(64), 128)  # CPU tensor: no fallback path
 
@@ -102,7 +102,7 @@ def test_ctypes_mirrors_have_the_layout_gcc_gives_the_header(hip, tmp_path):
     root = Path(__file__).resolve().parent.parent
     pairs = [("tbx_stage_t", hip.Stage), ("tbx_attn_seg_t", hip.AttnSeg), ("tbx_attn_t", hip.Attn), ("tbx_dec_mid_t", hip.DecMid), ("tbx_dec_layer_t", hip.DecLayer), ("tbx_heads_tail_t", hip.HeadsTail), ("tbx_knn_job_t", hip.KnnJob), ("tbx_pose_embed_job_t", hip.PoseEmbedJob), ("tbx_sim_state_t", hip.SimState),
              ("tbx_train_chain_t", hip.TrainChainArgs), ("tbx_rule_ctx_t", hip.RuleCtx), ("tbx_layer_tile_t", hip.LayerTile),
-             ("tbx_heads_tile_t", hip.HeadsTile), ("tbx_window_tile_t", hip.WindowTile), ("tbx_agent_prep_args_t", hip.AgentPrepArgs), ("tbx_front_t", hip.Front), ("tbx_tl_tail_t", hip.TlTail), ("tbx_pack_job_t", hip.PackJob),
+             ("tbx_heads_tile_t", hip.HeadsTile), ("tbx_window_tile_t", hip.WindowTile), ("tbx_agent_prep_args_t", hip.AgentPrepArgs), ("tbx_tl_rows_t", hip.TlRows), ("tbx_front_t", hip.Front), ("tbx_tl_tail_t", hip.TlTail), ("tbx_pack_job_t", hip.PackJob),
              ("tbx_drop_t", hip.Drop), ("tbx_linear_t", hip.Linear)]
     src = tmp_path / "sz.c"
     # ... and offsetof of every field (same names on both sides): runs of same-sized pointers keep sizeof when two fields swap
@@ -581,14 +581,14 @@ def test_host_descriptor_paths_read_their_host_arrays_in_bounds(hip):
         jb.idx, jb.invalid, jb.rel_pose, jb.emb = dp(8 * j + 4), dp(8 * j + 5), dp(8 * j + 6), None
         jb.n_batch, jb.n_src, jb.n_tgt, jb.tgt_batch_div, jb.k, jb.dist_limit = 1, n_src, n_tgt, 1, k, 1500.0
     for n in (1, 2, 3):
-        assert lib.tbx_knn_embed_multi(jobs, n, dp(40), dp(41), 128, None) < 0
-    assert lib.tbx_knn_embed_multi(jobs, 0, dp(40), dp(41), 128, None) == -1
+        assert lib.tbx_knn_embed_multi(jobs, n, dp(40), dp(41), 128, None, None) < 0
+    assert lib.tbx_knn_embed_multi(jobs, 0, dp(40), dp(41), 128, None, None) == -1
     jobs[1].k = 4096  # more neighbours than targets
-    assert lib.tbx_knn_embed_multi(jobs, 3, dp(40), dp(41), 128, None) < 0
+    assert lib.tbx_knn_embed_multi(jobs, 3, dp(40), dp(41), 128, None, None) < 0
     pe = hip.PoseEmbedJob()
     pe.pose3, pe.freqs_xy, pe.freqs_yaw, pe.out, pe.n, pe.pe_dim, pe.ld_out, pe.col_off = dp(50), dp(51), dp(52), dp(53), 64, 128, 128, 0
     jobs[1].k = 64
-    assert lib.tbx_knn_embed_multi_pe(jobs, 3, dp(40), dp(41), 128, C.byref(pe), None) < 0
+    assert lib.tbx_knn_embed_multi(jobs, 3, dp(40), dp(41), 128, C.byref(pe), None) < 0
     # a full stage program (MAX_STAGES entries) and one past it
     st = (hip.Stage * (hip.MAX_STAGES + 1))()
     for s in st:
@@ -622,7 +622,7 @@ def test_host_descriptor_paths_read_their_host_arrays_in_bounds(hip):
     assert lib.tbx_layernorm_bwd_add(dp(0), dp(1), dp(2), dp(3), dp(4), 16, 64, dp(5), dp(6), dp(7), dp(8), dp(9), None) < 0  # cols != 128
     assert lib.tbx_layernorm_bwd_add(dp(0), dp(1), dp(2), dp(3), dp(4), 16, 128, 0x10004, dp(6), dp(7), dp(8), dp(9), None) < 0  # misaligned `add`
     ss = hip.SimState()
-    assert lib.tbx_sim_step(C.byref(ss), None) == -1 and lib.tbx_sim_step_parts(C.byref(ss), 3, None) == -1
+    assert lib.tbx_sim_step(C.byref(ss), 7, None, None) == -1 and lib.tbx_sim_step(C.byref(ss), 3, None, None) == -1
     rc = hip.RuleCtx()
     assert lib.tbx_rule_check(C.byref(rc), dp(1), dp(2), dp(3), dp(4), 1, 0, 1, dp(5), None) == -1
 
@@ -717,3 +717,172 @@ def test_derived_weight_images_follow_the_weights_stamp_and_the_scope(tb):
         assert v.data_ptr() == w.data_ptr() and torch.equal(v, w) and vb.data_ptr() == bias.data_ptr() and torch.equal(vb, bias)
         assert v.data_ptr() >= flat.data_ptr() and vb.data_ptr() >= other.data_ptr()  # (the new storage)
     assert HB._at(owner._tbx_pack_plans["k"][1][0]) is w2  # a whole Parameter is rebuilt as itself
+
+
+# ---- the closed-loop step family: tbx_sim_step / tbx_agent_prep / tbx_tl_prep and the step tails of tbx_knarpe_dec_layer share their
+# checks (csrc/step_core.h). Descriptors of placeholder device addresses that are valid up to the launch: without a GPU the launch itself
+# fails (TBX_ERR_LAUNCH), which is how a test sees that every argument check passed.
+_ARG, _UNSUPPORTED, _ALIGN, _LAUNCH = -1, -2, -3, -4
+_dp = lambda i: 0x10000 * (i + 1)  # 16-byte aligned, distinct, never dereferenced on the host
+_STEP_W = 11                       # window of the step descriptors below
+
+
+def _no_gpu_only():
+    if torch.cuda.is_available():
+        pytest.skip("placeholder device addresses reach the launch: the no-GPU form of this test (a launch would dereference them)")
+
+
+def _sim_state(hip, n_ag=4, n_tl=3):
+    st = hip.SimState()
+    for i, (name, ty) in enumerate(hip.SimState._fields_):
+        if ty is C.c_void_p and not name.startswith(("ov_", "player_", "act_", "out_act_", "now_")):
+            setattr(st, name, _dp(100 + i))
+    st.n_batch, st.n_ag, st.n_tl, st.window, st.n_step_gt, st.n_step_tl_gt, st.n_step_out, st.n_node = 1, n_ag, n_tl, _STEP_W, 91, 91, 80, 20
+    return st
+
+
+def _prep_args(hip, n_tok=4, n_ag=4):
+    a = hip.AgentPrepArgs()
+    for i, (name, ty) in enumerate(hip.AgentPrepArgs._fields_):
+        if ty is C.c_void_p:
+            setattr(a, name, _dp(200 + i))
+    a.n_tok, a.n_ag, a.window, a.pe_dim, a.n_mp, a.mp_batch_div = n_tok, n_ag, _STEP_W, 64, 16, 1
+    return a
+
+
+def _tl_rows(hip):
+    return hip.TlRows(_dp(300), _dp(301), _dp(302), 16, 0)
+
+
+def _dec_layer(hip, n_rows):
+    """A last-layer tail_mfma32 tbx_knarpe_dec_layer descriptor of n_rows rows without a tail."""
+    t = hip.DecLayer()
+    m = t.mid
+    for i, name in enumerate(("qkv", "x", "rpe_k_bias_self", "rpe_k_bias_cross", "freqs_xy", "freqs_yaw", "fold_self_image", "out_proj_image",
+                              "q_image", "qfold_image", "fold_cross_image", "ln_weight", "ln_bias")):
+        setattr(m, name, _dp(400 + i))
+    for j, sg in enumerate((m.self_seg, m.cross_seg[0])):
+        sg.kv, sg.idx, sg.invalid, sg.rel_pose = (_dp(420 + 4 * j + q) for q in range(4))
+        sg.ld_kv, sg.k_off, sg.v_off, sg.n_tgt, sg.batch_div, sg.k = 256, 0, 128, 8, 1, 4
+    m.ld_qkv, m.q_off, m.qt_off, m.n_cross, m.n_batch, m.n_src = 896, 0, 384, 1, 1, n_rows
+    for i, name in enumerate(("out_proj2_image", "linear1_image", "linear2_image", "norm2_weight", "norm2_bias", "src_invalid")):
+        setattr(t, name, _dp(440 + i))
+    t.tail_mfma32 = 1
+    return t
+
+
+def _agents_tail(hip, sim, prep):
+    """(descriptor, keep-alive): the agents' step tail on (sim, prep) behind the heads."""
+    t = _dec_layer(hip, sim.n_batch * sim.n_ag)
+    h = hip.HeadsTail()
+    for i in range(9):
+        h.images[i] = _dp(500 + i)
+    for i, name in enumerate(("navi_emb", "latent_emb", "navi_valid", "latent_invalid", "type_mask")):
+        setattr(h, name, _dp(510 + i))
+    h.action_out, h.mask_stride = sim.action_mean, sim.n_batch * sim.n_ag
+    h.sim_parts, h.sim_state, h.next_prep = hip.SIM_AGENTS | hip.SIM_ADVANCE, C.addressof(sim), C.addressof(prep)
+    t.heads = C.addressof(h)
+    return t, (h, sim, prep)
+
+
+def _lights_tail(hip, sim, rows):
+    """(descriptor, keep-alive): the lights' step tail on sim, its riding rows = the fields of `rows`."""
+    t = _dec_layer(hip, sim.n_batch * sim.n_tl)
+    L = hip.TlTail()
+    for i in range(4):
+        L.kv_images[i], L.norm_weight[i], L.norm_bias[i] = _dp(600 + i), _dp(610 + i), _dp(620 + i)
+    for i in range(3):
+        L.mlp_images[i] = _dp(630 + i)
+    L.kv_out, L.tl_invalid, L.logits_out, L.ld_kv, L.n_state = _dp(640), rows.tl_invalid, sim.tl_logits, 1024, 5
+    L.sim_parts, L.sim_state = hip.SIM_LIGHTS | hip.SIM_ADVANCE, C.addressof(sim)
+    L.prep_attr, L.prep_row_invalid, L.prep_ld_attr = rows.attr, rows.row_invalid, rows.ld_attr
+    t.lights = C.addressof(L)
+    return t, (L, sim, rows)
+
+
+def _set(**kw):
+    def f(obj):
+        for k, v in kw.items():
+            setattr(obj, k, v)
+    return f
+
+
+def test_step_descriptors_are_valid_up_to_the_launch(hip):
+    """The descriptors the tests below break in one place each pass every argument check of every entry point that takes them."""
+    _no_gpu_only()
+    lib = hip.load()
+    assert lib.tbx_agent_prep(C.byref(_prep_args(hip)), None) == _LAUNCH
+    assert lib.tbx_tl_prep(_dp(0), 1, 3, _STEP_W, C.byref(_tl_rows(hip)), None) == _LAUNCH
+    assert lib.tbx_knarpe_dec_layer(C.byref(_dec_layer(hip, 4)), None) == _LAUNCH
+    t, keep = _agents_tail(hip, _sim_state(hip), _prep_args(hip))
+    assert lib.tbx_knarpe_dec_layer(C.byref(t), None) == _LAUNCH
+    t, keep = _lights_tail(hip, _sim_state(hip), _tl_rows(hip))
+    assert lib.tbx_knarpe_dec_layer(C.byref(t), None) == _LAUNCH
+
+
+@pytest.mark.parametrize("fault, code", [
+    (_set(window=24), _UNSUPPORTED), (_set(pe_dim=96), _UNSUPPORTED), (_set(ag_type_idx=None), _ARG), (_set(navi_row=None), _ARG),
+    (_set(n_ag=3), _UNSUPPORTED)], ids=["window-24", "pe_dim-96", "type_mask-without-ag_type_idx", "dest-without-navi_row", "n_tok-not-a-multiple-of-n_ag"])
+def test_agents_tail_refuses_what_agent_prep_refuses(hip, fault, code):
+    """tbx_agent_prep and the agents' step tail of tbx_knarpe_dec_layer on the same tbx_agent_prep_args_t: the same code."""
+    _no_gpu_only()
+    lib = hip.load()
+    sim, prep = _sim_state(hip), _prep_args(hip)
+    t, keep = _agents_tail(hip, sim, prep)
+    assert lib.tbx_agent_prep(C.byref(prep), None) == _LAUNCH and lib.tbx_knarpe_dec_layer(C.byref(t), None) == _LAUNCH
+    fault(prep)
+    assert lib.tbx_agent_prep(C.byref(prep), None) == code
+    assert lib.tbx_knarpe_dec_layer(C.byref(t), None) == code
+
+
+@pytest.mark.parametrize("fault, code, float4_only", [
+    (_set(attr=None), _ARG, False), (_set(ld_attr=5 + _STEP_W - 1), _ARG, False), (_set(ld_attr=18), _ALIGN, False),
+    (_set(attr=_dp(301) + 4), _ALIGN, True)], ids=["attr-null", "ld_attr-below-5+window", "ld_attr-not-a-multiple-of-4", "attr-misaligned"])
+def test_every_writer_of_the_lights_rows_checks_them_alike(hip, fault, code, float4_only):
+    """tbx_sim_step with tl_rows, the lights' step tail of tbx_knarpe_dec_layer and (but for the alignment, which only the float4
+    stores of the riding forms need) tbx_tl_prep on the same rows: the same code."""
+    _no_gpu_only()
+    lib = hip.load()
+    sim, rows = _sim_state(hip), _tl_rows(hip)
+    parts = hip.SIM_LIGHTS | hip.SIM_ADVANCE
+    assert lib.tbx_sim_step(C.byref(sim), parts, C.byref(rows), None) == _LAUNCH
+    fault(rows)
+    t, keep = _lights_tail(hip, sim, rows)
+    assert lib.tbx_sim_step(C.byref(sim), parts, C.byref(rows), None) == code
+    assert lib.tbx_knarpe_dec_layer(C.byref(t), None) == code
+    assert lib.tbx_tl_prep(_dp(0), 1, 3, _STEP_W, C.byref(rows), None) == (_LAUNCH if float4_only else code)
+
+
+@pytest.mark.parametrize("fault", [
+    _set(hist_tl=None), _set(dest_thresh=None), _set(player_valid=_dp(700)), _set(act_seed=_dp(701), out_act_noise=_dp(702))], ids=["lights-pointer-null", "agents-pointer-null", "player_valid-without-player_action", "act_seed-without-out_act_log_prob"])
+def test_step_tails_refuse_the_state_sim_step_refuses(hip, fault):
+    """tbx_sim_step and the step tails of tbx_knarpe_dec_layer on the same tbx_sim_state_t: the same code. The rule is the full list of
+    the stand-alone call whatever the parts, so either side's pointer is missed by both tails and by every choice of parts."""
+    _no_gpu_only()
+    lib = hip.load()
+    sim = _sim_state(hip)
+    ta, keep_a = _agents_tail(hip, sim, _prep_args(hip))
+    tl, keep_l = _lights_tail(hip, sim, _tl_rows(hip))
+    assert lib.tbx_knarpe_dec_layer(C.byref(ta), None) == _LAUNCH and lib.tbx_knarpe_dec_layer(C.byref(tl), None) == _LAUNCH
+    fault(sim)
+    for parts in (hip.SIM_AGENTS | hip.SIM_LIGHTS | hip.SIM_ADVANCE, hip.SIM_AGENTS | hip.SIM_ADVANCE, hip.SIM_LIGHTS):
+        assert lib.tbx_sim_step(C.byref(sim), parts, None, None) == _ARG
+    assert lib.tbx_knarpe_dec_layer(C.byref(ta), None) == _ARG and lib.tbx_knarpe_dec_layer(C.byref(tl), None) == _ARG
+
+
+def test_sim_step_parts_grammar_of_the_one_entry_point(hip):
+    """The four call shapes the three former entry points had - the whole step, one side, TBX_SIM_APPEND alone, the lights with their
+    rows riding - are accepted up to the launch; what they refused is still TBX_ERR_ARG."""
+    _no_gpu_only()
+    lib = hip.load()
+    sim, rows = _sim_state(hip), _tl_rows(hip)
+    A, L, ADV, NO_DIS, NO_APP, APP = hip.SIM_AGENTS, hip.SIM_LIGHTS, hip.SIM_ADVANCE, hip.SIM_NO_DISABLE, hip.SIM_NO_APPEND, hip.SIM_APPEND
+    step = lambda parts, r=None: lib.tbx_sim_step(C.byref(sim), parts, C.byref(r) if r is not None else None, None)
+    for parts in (A | L | ADV, A, L, A | ADV, L | ADV, ADV, APP, A | L | ADV | NO_DIS | NO_APP):
+        assert step(parts) == _LAUNCH, parts
+    for parts in (L, L | ADV, A | L | ADV):
+        assert step(parts, rows) == _LAUNCH, parts
+    for parts in (APP | A, NO_DIS, NO_APP, NO_DIS | ADV, 0, 64):
+        assert step(parts) == _ARG, parts
+    for parts in (A, A | ADV, APP, L | NO_APP):  # rows without the lights' part, or with windows that are left alone
+        assert step(parts, rows) == _ARG, parts

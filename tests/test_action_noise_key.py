@@ -109,6 +109,6 @@ def test_zero_initialised_state_has_sampling_off_and_a_seed_needs_its_logs(tb):
             setattr(st, name, 64)
     st.n_batch = st.n_ag = st.n_tl = st.window = st.n_step_out = st.n_node = 1
     st.act_seed = 64
-    assert lib.tbx_sim_step_parts(C.byref(st), hip.SIM_AGENTS, None) == -1
+    assert lib.tbx_sim_step(C.byref(st), hip.SIM_AGENTS, None, None) == -1
     st.out_act_noise = 64
-    assert lib.tbx_sim_step_parts(C.byref(st), hip.SIM_AGENTS, None) == -1
+    assert lib.tbx_sim_step(C.byref(st), hip.SIM_AGENTS, None, None) == -1

@@ -906,7 +906,7 @@ def test_window_tile_equals_grouped_chain(tb, hip, dev, G, W):
 @pytest.mark.parametrize("G,W,add,rider_rows,knn", [(64, 11, False, 64, True), (37, 11, False, 21, True), (128, 11, True, 0, False), (5, 7, False, 0, True)])
 def test_front_equals_its_three_launches(tb, hip, dev, G, W, add, rider_rows, knn):
     """tbx_front - window PointNet + the first projection of its pooled rows (+ rider) + K-nearest searches and pose-embedding job in
-    ONE launch (csrc/front.hip) - against tbx_window_tile -> tbx_layer_tile (rider) and tbx_knn_embed_multi_pe as launches of their
+    ONE launch (csrc/front.hip) - against tbx_window_tile -> tbx_layer_tile (rider) and tbx_knn_embed_multi as launches of their
     own: the same device functions on the same operands, so pooled rows, q | k | v | W_k^T q rows, rider rows, K-nearest indices /
     masks / relative poses and the embedded poses are bit-identical; odd window counts (a ragged last workgroup), a rider whose row
     count differs from the windows', the lights' "add" mode without searches, a launch smaller than one rider tile."""

@@ -272,7 +272,7 @@ def test_joint_future_pred_shares_map_and_matches_single(tb):
 
 
 def test_lights_one_step_ahead_equals_sequential_order(tb):
-    """The engine advances the traffic lights one step ahead on a second stream (tbx_sim_step_parts): every kernel sees
+    """The engine advances the traffic lights one step ahead on a second stream (tbx_sim_step by parts): every kernel sees
     the inputs of the sequential order, so the rollout must be bit-identical to it, eager and as a graph."""
     dev = torch.device("cuda:0")
     wm, P, b, bd = _setup(tb, dev, (8, 64, 8), 4)

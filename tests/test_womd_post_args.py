@@ -29,7 +29,7 @@ def test_new_symbols_are_declared_and_exported(tb, lib):
     hip = import_module("trafficbots_amd.hip")
     for s in ("tbx_womd_modes", "tbx_pose_to_global"):
         assert s in hip.declared_symbols() and hasattr(lib, s) and getattr(lib, s).argtypes is not None
-    assert lib.tbx_version() == 6  # (the entry points here were added without a bump; 6 = tbx_drop_t / tbx_linear_t)
+    assert lib.tbx_version() == 7  # (the entry points here were added without a bump; 7 = the closed-loop step family)
     assert callable(hip.womd_modes) and callable(hip.pose_to_global)
 
 

@@ -97,6 +97,11 @@ class AgentPrepArgs(C.Structure):
                 + [(n, C.c_int32) for n in ("n_tok", "n_ag", "window", "pe_dim", "n_mp", "mp_batch_div")])
 
 
+class TlRows(C.Structure):
+    """tbx_tl_rows_t (include/tbx_hip.h)."""
+    _fields_ = [("tl_invalid", C.c_void_p), ("attr", C.c_void_p), ("row_invalid", C.c_void_p), ("ld_attr", C.c_int32), ("pad_", C.c_int32)]
+
+
 class DecLayer(C.Structure):
     """tbx_dec_layer_t (include/tbx_hip.h)."""
     _fields_ = ([("mid", DecMid)]
@@ -173,7 +178,7 @@ class SimState(C.Structure):
         + [(n, C.c_float) for n in ("w_pos", "w_rot", "w_spd")]
         + [(n, C.c_void_p) for n in ("player_valid", "player_action", "ov_valid", "ov_pose", "ov_motion", "ov_tl_valid",
                                      "ov_tl_state", "now_outside", "now_reached")]
-        # sampled actions (act_seed NULL = off): appended without a version bump, see the header
+        # sampled actions (act_seed NULL = off)
         + [("act_seed", C.c_void_p), ("act_log_std", (C.c_float * 2) * 3), ("out_act_noise", C.c_void_p), ("out_act_log_prob", C.c_void_p)]
     )
 
@@ -233,8 +238,7 @@ def load():
     lib.tbx_knarpe_attn_bwd.argtypes = [C.POINTER(Attn), vp]
     lib.tbx_knarpe_dec_mid.argtypes = [C.POINTER(DecMid), vp]
     lib.tbx_knarpe_dec_layer.argtypes = [C.POINTER(DecLayer), vp]
-    lib.tbx_knn_embed_multi.argtypes = [C.POINTER(KnnJob), i32, vp, vp, i32, vp]
-    lib.tbx_knn_embed_multi_pe.argtypes = [C.POINTER(KnnJob), i32, vp, vp, i32, C.POINTER(PoseEmbedJob), vp]
+    lib.tbx_knn_embed_multi.argtypes = [C.POINTER(KnnJob), i32, vp, vp, i32, C.POINTER(PoseEmbedJob), vp]
     lib.tbx_keyed_dropout.argtypes = [vp, vp, i64, i32, C.POINTER(Drop), vp]
     lib.tbx_linear_wgrad_splits.argtypes = [i64, i32, i32]
     lib.tbx_linear_wgrad.argtypes = [vp, i32, vp, i32, i64, i32, i32, vp, vp, vp, i32, vp]
@@ -283,13 +287,10 @@ def load():
     lib.tbx_rowchain_live.argtypes = [C.POINTER(Stage), i32, i64, i32, i32, i32, i32, vp]
     lib.tbx_rowchain.argtypes = [C.POINTER(Stage), i32, i64, i32, i32, i32, vp]
     lib.tbx_rowchain_ex.argtypes = [C.POINTER(Stage), i32, i64, i32, i32, i32, i32, i32, vp]
-    lib.tbx_agent_prep.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32,
-                                   i32, vp, vp, vp]
-    lib.tbx_tl_prep.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.tbx_agent_prep.argtypes = [C.POINTER(AgentPrepArgs), vp]
+    lib.tbx_tl_prep.argtypes = [vp, i32, i32, i32, C.POINTER(TlRows), vp]
     lib.tbx_map_prep.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.tbx_sim_step.argtypes = [C.POINTER(SimState), vp]
-    lib.tbx_sim_step_parts.argtypes = [C.POINTER(SimState), i32, vp]
-    lib.tbx_sim_step_tl_prep.argtypes = [C.POINTER(SimState), i32, vp, i32, vp, vp, vp]
+    lib.tbx_sim_step.argtypes = [C.POINTER(SimState), i32, C.POINTER(TlRows), vp]
     lib.tbx_rule_tables.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.tbx_rule_grid.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.tbx_rule_grid_cells.argtypes = []
@@ -302,11 +303,11 @@ def load():
     lib.tbx_attn_fold_fwd.argtypes = [vp] * 14
     lib.tbx_attn_fold_bwd.argtypes = [vp] * 19
     lib.tbx_rule_navi_check.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    for name in ("tbx_layer_tile", "tbx_heads_tile", "tbx_window_tile", "tbx_front", "tbx_tall_linear", "tbx_pack_weight_mfma32", "tbx_pack_weight_mfma32_multi", "tbx_pack_weight", "tbx_pack_weight_split", "tbx_pack_weight_gemv", "tbx_rowchain_live", "tbx_knarpe_dec_mid", "tbx_knarpe_dec_layer", "tbx_knn_embed_multi", "tbx_knn_embed_multi_pe", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd", "tbx_knarpe_attn_bwd", "tbx_keyed_dropout", "tbx_linear_wgrad_splits", "tbx_linear_wgrad", "tbx_linear_wgrad_bf16", "tbx_tall_linear_bf16", "tbx_tl_tail_tile", "tbx_tl_tail_tile_bf16", "tbx_layernorm_fwd", "tbx_layernorm_bwd_partials", "tbx_layernorm_bwd", "tbx_layernorm_bwd_add", "tbx_residual_drop_fwd", "tbx_residual_drop_bwd", "tbx_relu_drop_fwd", "tbx_relu_drop_bwd", "tbx_pair_bias_relu", "tbx_pointnet_tail_fwd", "tbx_pointnet_tail_bwd", "tbx_masked_maxpool_fwd", "tbx_masked_maxpool_bwd", "tbx_train_chain_fwd", "tbx_train_chain_fwd_windows", "tbx_train_chain_bwd", "tbx_knn_inverse", "tbx_rowchain", "tbx_rowchain_ex", "tbx_agent_prep", "tbx_tl_prep",
-                 "tbx_map_prep", "tbx_sim_step", "tbx_sim_step_parts", "tbx_sim_step_tl_prep", "tbx_rule_tables", "tbx_rule_grid", "tbx_rule_grid_cells", "tbx_rule_check", "tbx_rule_accumulate", "tbx_filter_futures", "tbx_rule_navi_check", "tbx_attn_fold_fwd", "tbx_attn_fold_bwd", "tbx_front_pair", "tbx_knarpe_dec_layer_pair",
+    for name in ("tbx_layer_tile", "tbx_heads_tile", "tbx_window_tile", "tbx_front", "tbx_tall_linear", "tbx_pack_weight_mfma32", "tbx_pack_weight_mfma32_multi", "tbx_pack_weight", "tbx_pack_weight_split", "tbx_pack_weight_gemv", "tbx_rowchain_live", "tbx_knarpe_dec_mid", "tbx_knarpe_dec_layer", "tbx_knn_embed_multi", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd", "tbx_knarpe_attn_bwd", "tbx_keyed_dropout", "tbx_linear_wgrad_splits", "tbx_linear_wgrad", "tbx_linear_wgrad_bf16", "tbx_tall_linear_bf16", "tbx_tl_tail_tile", "tbx_tl_tail_tile_bf16", "tbx_layernorm_fwd", "tbx_layernorm_bwd_partials", "tbx_layernorm_bwd", "tbx_layernorm_bwd_add", "tbx_residual_drop_fwd", "tbx_residual_drop_bwd", "tbx_relu_drop_fwd", "tbx_relu_drop_bwd", "tbx_pair_bias_relu", "tbx_pointnet_tail_fwd", "tbx_pointnet_tail_bwd", "tbx_masked_maxpool_fwd", "tbx_masked_maxpool_bwd", "tbx_train_chain_fwd", "tbx_train_chain_fwd_windows", "tbx_train_chain_bwd", "tbx_knn_inverse", "tbx_rowchain", "tbx_rowchain_ex", "tbx_agent_prep", "tbx_tl_prep",
+                 "tbx_map_prep", "tbx_sim_step", "tbx_rule_tables", "tbx_rule_grid", "tbx_rule_grid_cells", "tbx_rule_check", "tbx_rule_accumulate", "tbx_filter_futures", "tbx_rule_navi_check", "tbx_attn_fold_fwd", "tbx_attn_fold_bwd", "tbx_front_pair", "tbx_knarpe_dec_layer_pair",
                  "tbx_womd_modes", "tbx_pose_to_global", "tbx_rel_pose_dense", "tbx_diffbar_reward", "tbx_knarpe_attn_fwd_mfma"):
         getattr(lib, name).restype = C.c_int
-    if lib.tbx_version() != 6:
+    if lib.tbx_version() != 7:
         raise ImportError("libtbx_hip.so ABI version mismatch")
     # (an entry point without argtypes would get 64-bit handles - stream pointers under graph capture - as C ints)
     untyped = [s for s in declared_symbols() if getattr(lib, s).argtypes is None and s not in ("tbx_error_string", "tbx_version")]

@@ -645,8 +645,9 @@ static int dec_fill(const tbx_dec_mid_t* p, const tbx_dec_layer_t* t, MidArgs& a
         a.sim = *h.sim_state, a.prep = *h.next_prep, a.sim_parts = h.sim_parts, a.fused_tail = 1;
         if ((a.sim_parts & ~TBX_SIM_ADVANCE) != TBX_SIM_AGENTS) return TBX_ERR_ARG;
         if (a.sim.n_batch * a.sim.n_ag != a.n_rows || a.prep.n_tok != a.n_rows || a.sim.action_mean != h.action_out) return TBX_ERR_ARG;
-        if (!a.sim.step || !a.prep.hist_valid || !a.prep.tok_pose || !a.prep.attr || !a.prep.pe || !a.prep.row_invalid) return TBX_ERR_ARG;
-        if (!tbx_step::sim_sampling_ok(a.sim)) return TBX_ERR_ARG;
+        int rc = tbx_step::sim_state_ok(a.sim);  // (the stand-alone calls' checks, step_core.h)
+        if (rc == TBX_OK) rc = tbx_step::agent_prep_ok(a.prep);
+        if (rc != TBX_OK) return rc;
         a.sim_parts = tbx_step::sim_kernel_parts(a.sim, a.sim_parts);
       }
     }
@@ -665,9 +666,10 @@ static int dec_fill(const tbx_dec_mid_t* p, const tbx_dec_layer_t* t, MidArgs& a
         a.sim = *L.sim_state, a.sim_parts = L.sim_parts, a.tl_sim = 1;
         if ((a.sim_parts & ~(TBX_SIM_ADVANCE | TBX_SIM_NO_APPEND)) != TBX_SIM_LIGHTS) return TBX_ERR_ARG;
         if (a.sim.n_batch * a.sim.n_tl != a.n_rows || a.sim.tl_logits != L.logits_out || L.n_state != 5) return TBX_ERR_ARG;
-        if (!a.sim.step || !a.sim.tl_state || !a.sim.hist_tl || !a.sim.tl_gt || !a.sim.out_tl_state) return TBX_ERR_ARG;
-        if (!L.prep_attr || !L.prep_row_invalid || L.prep_ld_attr < 16 || (L.prep_ld_attr % 4) || (((uintptr_t)L.prep_attr) & 15)) return TBX_ERR_ARG;
-        a.tl_prep = tbx_step::TlPrepArgs{L.tl_invalid, L.prep_attr, L.prep_row_invalid, L.prep_ld_attr};
+        a.tl_prep = tbx_step::TlPrepArgs{{L.tl_invalid, L.prep_attr, L.prep_row_invalid, L.prep_ld_attr, 0}};
+        int rc = tbx_step::sim_state_ok(a.sim);  // (tbx_sim_step's checks of the state and of the riding rows, step_core.h)
+        if (rc == TBX_OK) rc = tbx_step::tl_rows_ok(a.tl_prep, a.sim.window, true);
+        if (rc != TBX_OK) return rc;
       }
     }
   }

@@ -1,6 +1,6 @@
 // tbx_front: everything between tbx_agent_prep / tbx_tl_prep and a block's first decoder layer as ONE launch, for the closed loop at a
 // few scenes (launches of <= 1024 windows). It replaced three dependent launches on the critical path of every step - the window
-// PointNet (tbx_window_tile: 8 us), the K-nearest searches (tbx_knn_embed_multi_pe: 13 us) and the block's first projection
+// PointNet (tbx_window_tile: 8 us), the K-nearest searches (tbx_knn_embed_multi: 13 us) and the block's first projection
 // (tbx_layer_tile + rider: 7 us) - whose work is independent or per-window:
 //   window workgroups (2 windows each, csrc/window_core.h): the temporal PointNet, then - the two pooled rows never leave the CU -
 //     LayerNorm + q | k | v = in_proj(norm x) + qt = W_rpe_k^T q of the first layer (transformer_rpe.py:207-211, attention_rpe.py:92-98,147)

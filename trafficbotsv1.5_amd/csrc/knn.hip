@@ -70,12 +70,7 @@ extern "C" int tbx_knn_embed(const float* src_pose, const uint8_t* src_invalid, 
 }
 
 extern "C" int tbx_knn_embed_multi(const tbx_knn_job_t* jobs, int n_jobs, const float* freqs_xy, const float* freqs_yaw, int pe_dim,
-                                   void* stream) {
-  return tbx_knn_embed_multi_pe(jobs, n_jobs, freqs_xy, freqs_yaw, pe_dim, nullptr, stream);
-}
-
-extern "C" int tbx_knn_embed_multi_pe(const tbx_knn_job_t* jobs, int n_jobs, const float* freqs_xy, const float* freqs_yaw, int pe_dim,
-                                      const tbx_pose_embed_job_t* pe, void* stream) {
+                                   const tbx_pose_embed_job_t* pe, void* stream) {
   KnnMulti m;
   int blocks = 0;
   const int rc = tbx_knn::knn_multi_fill(jobs, n_jobs, freqs_xy, freqs_yaw, pe_dim, pe, m, blocks);

@@ -143,7 +143,7 @@ __device__ __forceinline__ void knn_rows(const KnnArgs& a, int block) {
 // launches on the auxiliary stream). A workgroup = one source row of one job (the 4-waves-per-row form); jobs are laid out
 // back to back over blockIdx.x in the order given (the longest search first, so that its rows are dispatched first).
 constexpr int KNN_MAX_JOBS = 4;
-struct PoseEmbedArgs {  // tbx_pose_embed riding on the searches' launch (tbx_knn_embed_multi_pe): the blocks past the last search
+struct PoseEmbedArgs {  // tbx_pose_embed riding on the searches' launch (tbx_knn_embed_multi's pe): the blocks past the last search
   const float* pose3;
   const float *fxy, *fyaw;
   float* out;
@@ -181,7 +181,7 @@ __device__ __forceinline__ void knn_multi_body(const KnnMulti& m, const int bid)
 }
 
 
-// host: the launch descriptor of tbx_knn_embed_multi_pe's arguments; blocks = its workgroups (256 threads each)
+// host: the launch descriptor of tbx_knn_embed_multi's arguments; blocks = its workgroups (256 threads each)
 inline int knn_multi_fill(const tbx_knn_job_t* jobs, int n_jobs, const float* freqs_xy, const float* freqs_yaw, int pe_dim,
                           const tbx_pose_embed_job_t* pe, KnnMulti& m, int& blocks) {
   if (!jobs || n_jobs <= 0 || n_jobs > KNN_MAX_JOBS) return TBX_ERR_ARG;

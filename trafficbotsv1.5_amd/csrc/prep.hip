@@ -94,21 +94,11 @@ __global__ void map_prep_kernel(const uint8_t* __restrict__ mp_valid, const floa
 
 }  // namespace
 
-extern "C" int tbx_agent_prep(const uint8_t* hist_valid, const float* hist_pose, const float* hist_motion,
-                              const float* ag_attr6, const uint8_t* ag_type_idx, int n_batch, int n_ag, int window,
-                              const float* freqs_xy, const float* freqs_yaw, int pe_dim, float* tok_pose,
-                              uint8_t* tok_invalid, float* attr, float* pe, uint8_t* row_invalid, uint8_t* type_mask,
-                              const int64_t* dest, const float* mp_tok_pose, int n_mp, int mp_batch_div, float* navi_pose3,
-                              int32_t* navi_row, void* stream) {
-  if (!hist_valid || !hist_pose || !hist_motion || !ag_attr6 || !freqs_xy || !freqs_yaw || !tok_pose || !tok_invalid ||
-      !attr || !pe || !row_invalid)
-    return TBX_ERR_ARG;
-  if (n_batch <= 0 || n_ag <= 0 || window <= 0 || window > 23 || (pe_dim != 64 && pe_dim != 128)) return TBX_ERR_UNSUPPORTED;
-  if (type_mask != nullptr && !ag_type_idx) return TBX_ERR_ARG;
-  if (dest != nullptr && (!mp_tok_pose || !navi_pose3 || !navi_row || n_mp <= 0 || mp_batch_div <= 0)) return TBX_ERR_ARG;
-  AgentPrepArgs a{hist_valid, hist_pose, hist_motion, ag_attr6, ag_type_idx, freqs_xy, freqs_yaw, tok_pose, tok_invalid,
-                  attr, pe, row_invalid, type_mask, dest, mp_tok_pose, navi_pose3, navi_row, n_batch * n_ag, n_ag, window,
-                  pe_dim, n_mp, mp_batch_div};
+extern "C" int tbx_agent_prep(const tbx_agent_prep_args_t* args, void* stream) {
+  if (!args) return TBX_ERR_ARG;
+  const int rc = tbx_step::agent_prep_ok(*args);
+  if (rc != TBX_OK) return rc;
+  const AgentPrepArgs& a = *args;
   static const int wave_rows = [] {
     const char* e = getenv("TBX_PREP_WAVE_ROWS");
     return e && atoi(e) > 0 ? atoi(e) : 512;
@@ -120,13 +110,13 @@ extern "C" int tbx_agent_prep(const uint8_t* hist_valid, const float* hist_pose,
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 
-extern "C" int tbx_tl_prep(const uint8_t* hist_tl, const uint8_t* tl_invalid, int n_batch, int n_tl, int window,
-                           int ld_attr, float* attr, uint8_t* row_invalid, void* stream) {
-  if (!hist_tl || !tl_invalid || !attr || !row_invalid || n_batch <= 0 || n_tl <= 0 || window <= 0) return TBX_ERR_ARG;
-  if (ld_attr < 5 + window || ld_attr % 4) return TBX_ERR_UNSUPPORTED;
-  const int64_t rows = (int64_t)n_batch * n_tl * window;
-  hipLaunchKernelGGL(tl_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, hist_tl,
-                     tl_invalid, n_batch * n_tl, window, ld_attr, attr, row_invalid);
+extern "C" int tbx_tl_prep(const uint8_t* hist_tl, int n_batch, int n_tl, int window, const tbx_tl_rows_t* rows, void* stream) {
+  if (!hist_tl || !rows || n_batch <= 0 || n_tl <= 0 || window <= 0) return TBX_ERR_ARG;
+  const int rc = tbx_step::tl_rows_ok(*rows, window, false);
+  if (rc != TBX_OK) return rc;
+  const int64_t n_rows = (int64_t)n_batch * n_tl * window;
+  hipLaunchKernelGGL(tl_prep_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, hist_tl,
+                     rows->tl_invalid, n_batch * n_tl, window, rows->ld_attr, rows->attr, rows->row_invalid);
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 

@@ -63,38 +63,21 @@ __global__ void sim_append_kernel(const tbx_sim_state_t s) {
 
 }  // namespace
 
-extern "C" int tbx_sim_step(const tbx_sim_state_t* st, void* stream) {
-  return tbx_sim_step_parts(st, TBX_SIM_AGENTS | TBX_SIM_LIGHTS | TBX_SIM_ADVANCE, stream);
-}
-
-extern "C" int tbx_sim_step_parts(const tbx_sim_state_t* st, int parts, void* stream) {
-  return tbx_sim_step_tl_prep(st, parts, nullptr, 0, nullptr, nullptr, stream);
-}
-
-extern "C" int tbx_sim_step_tl_prep(const tbx_sim_state_t* st, int parts, const uint8_t* tl_invalid, int ld_attr, float* attr,
-                                    uint8_t* row_invalid, void* stream) {
-  TlPrepArgs tp{nullptr, nullptr, nullptr, 0};
-  if (tl_invalid != nullptr) {
-    if (!st || !(parts & TBX_SIM_LIGHTS) || (parts & TBX_SIM_NO_APPEND) || !attr || !row_invalid || ld_attr < 5 + st->window) return TBX_ERR_ARG;
-    if ((ld_attr % 4) || (((uintptr_t)attr) & 15)) return TBX_ERR_ALIGN;  // rows are written as float4
-    tp = TlPrepArgs{tl_invalid, attr, row_invalid, ld_attr};
+extern "C" int tbx_sim_step(const tbx_sim_state_t* st, int parts, const tbx_tl_rows_t* tl_rows, void* stream) {
+  TlPrepArgs tp{};
+  if (tl_rows != nullptr) {  // the lights' new rows ride on their (appending) update
+    if (!st || !(parts & TBX_SIM_LIGHTS) || (parts & TBX_SIM_NO_APPEND)) return TBX_ERR_ARG;
+    const int rc = tbx_step::tl_rows_ok(*tl_rows, st->window, true);
+    if (rc != TBX_OK) return rc;
+    tp = TlPrepArgs{*tl_rows};
   }
   const int known = TBX_SIM_AGENTS | TBX_SIM_LIGHTS | TBX_SIM_ADVANCE | TBX_SIM_NO_DISABLE | TBX_SIM_NO_APPEND | TBX_SIM_APPEND;
   if (!st || (parts & ~known) || parts == 0) return TBX_ERR_ARG;
   if ((parts & TBX_SIM_APPEND) && parts != TBX_SIM_APPEND) return TBX_ERR_ARG;  // a part of its own
   if ((parts & (TBX_SIM_NO_DISABLE | TBX_SIM_NO_APPEND)) && !(parts & (TBX_SIM_AGENTS | TBX_SIM_LIGHTS))) return TBX_ERR_ARG;
   const tbx_sim_state_t& s = *st;
-  if (s.n_batch <= 0 || s.n_ag <= 0 || s.n_tl <= 0 || s.window <= 0 || s.n_step_out <= 0 || s.n_node <= 0) return TBX_ERR_ARG;
-  const void* need[] = {s.step, s.ag_valid, s.ag_disabled, s.ag_pose, s.ag_motion, s.navi_valid, s.outside_map,
-                        s.dest_reached, s.tl_state, s.hist_valid, s.hist_pose, s.hist_motion, s.hist_tl, s.ag_type_idx,
-                        s.tf_mask, s.gt_valid, s.gt_pose, s.gt_motion, s.tl_gt, s.boundary, s.dest_pos, s.dest_dir,
-                        s.dest_invalid, s.dest_kind, s.dest_thresh, s.action_mean, s.tl_logits, s.out_valid, s.out_pose,
-                        s.out_motion, s.out_action, s.out_tl_state, s.out_outside_map, s.out_dest_reached};
-  for (const void* p : need)
-    if (p == nullptr) return TBX_ERR_ARG;
-  if (s.player_valid != nullptr && s.player_action == nullptr) return TBX_ERR_ARG;
-  if (s.ov_valid != nullptr && (!s.ov_pose || !s.ov_motion || !s.ov_tl_valid || !s.ov_tl_state)) return TBX_ERR_ARG;
-  if (!tbx_step::sim_sampling_ok(s)) return TBX_ERR_ARG;  // sampled actions: the seed with both of its logs
+  const int rc = tbx_step::sim_state_ok(s);
+  if (rc != TBX_OK) return rc;
   if (parts == TBX_SIM_APPEND) {
     const int64_t na = (int64_t)s.n_batch * (s.n_ag > s.n_tl ? s.n_ag : s.n_tl);
     hipLaunchKernelGGL(sim_append_kernel, dim3((unsigned)((na + 127) / 128)), dim3(128), 0, (hipStream_t)stream, s);

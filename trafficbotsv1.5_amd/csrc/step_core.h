@@ -41,6 +41,28 @@ struct SimLoads {
 // tbx_sim_state_t's sampled-action group (host side): off, or complete
 inline bool sim_sampling_ok(const tbx_sim_state_t& s) { return s.act_seed == nullptr || (s.out_act_noise != nullptr && s.out_act_log_prob != nullptr); }
 
+// A simulation state any part may run on (host side): tbx_sim_step's check and, for their sim_state, the check of both step tails of
+// tbx_knarpe_dec_layer / _pair. The FULL list whatever the parts: every descriptor the rollout engine hands to a tail is a copy of
+// the one state its stand-alone calls take. First failure wins; every one is TBX_ERR_ARG:
+//   1  a size (n_batch, n_ag, n_tl, window, n_step_out, n_node) <= 0
+//   2  a required pointer NULL (step .. out_dest_reached: everything above max_acc in the struct)
+//   3  player_valid without player_action
+//   4  ov_valid without ov_pose, ov_motion, ov_tl_valid, ov_tl_state
+//   5  act_seed without out_act_noise, out_act_log_prob (sim_sampling_ok)
+inline int sim_state_ok(const tbx_sim_state_t& s) {
+  if (s.n_batch <= 0 || s.n_ag <= 0 || s.n_tl <= 0 || s.window <= 0 || s.n_step_out <= 0 || s.n_node <= 0) return TBX_ERR_ARG;
+  const void* need[] = {s.step, s.ag_valid, s.ag_disabled, s.ag_pose, s.ag_motion, s.navi_valid, s.outside_map,
+                        s.dest_reached, s.tl_state, s.hist_valid, s.hist_pose, s.hist_motion, s.hist_tl, s.ag_type_idx,
+                        s.tf_mask, s.gt_valid, s.gt_pose, s.gt_motion, s.tl_gt, s.boundary, s.dest_pos, s.dest_dir,
+                        s.dest_invalid, s.dest_kind, s.dest_thresh, s.action_mean, s.tl_logits, s.out_valid, s.out_pose,
+                        s.out_motion, s.out_action, s.out_tl_state, s.out_outside_map, s.out_dest_reached};
+  for (const void* p : need)
+    if (p == nullptr) return TBX_ERR_ARG;
+  if (s.player_valid != nullptr && s.player_action == nullptr) return TBX_ERR_ARG;
+  if (s.ov_valid != nullptr && (!s.ov_pose || !s.ov_motion || !s.ov_tl_valid || !s.ov_tl_state)) return TBX_ERR_ARG;
+  return sim_sampling_ok(s) ? TBX_OK : TBX_ERR_ARG;
+}
+
 // Internal bit of a kernel's `parts` (never in a caller's: the entry points refuse unknown bits, then set it themselves): the state has
 // sampled actions on (act_seed != NULL). The sampled bodies below branch on THIS - a scalar every form holds already - rather than on
 // the pointer in the kernel-argument segment.
@@ -319,13 +341,24 @@ __device__ __forceinline__ void sim_advance(const tbx_sim_state_t& s, const int 
   }
 }
 
-// tbx_tl_prep of the lights' new windows riding on their update (tbx_sim_step_tl_prep): a light's lanes write its own W rows
-struct TlPrepArgs {
-  const uint8_t* tl_invalid;  // NULL: off
-  float* attr;
-  uint8_t* row_invalid;
-  int ld_attr;
-};
+// tbx_tl_prep of the lights' new windows riding on their update (tbx_sim_step's tl_rows): a light's lanes write its own W rows.
+// tl_invalid NULL: off. tbx_tl_rows_t under the name sim_step_kernel's symbol carries (a typedef would rename the kernel: the device
+// code of this change is the parent's byte for byte, symbols included)
+struct TlPrepArgs : tbx_tl_rows_t {};
+static_assert(sizeof(TlPrepArgs) == sizeof(tbx_tl_rows_t), "the public struct is the kernel argument");
+
+// The lights' attribute rows (host side): the check of tbx_tl_prep, of tbx_sim_step's tl_rows and of the lights' step tail (which
+// builds the struct from tbx_tl_tail_t's tl_invalid / prep_* fields). float4_rows: the riding forms, whose rows are float4 stores.
+// First failure wins:
+//   1  tl_invalid, attr or row_invalid NULL      TBX_ERR_ARG
+//   2  ld_attr < 5 + window                      TBX_ERR_ARG
+//   3  ld_attr % 4                               TBX_ERR_ALIGN
+//   4  float4_rows: attr not 16-byte aligned     TBX_ERR_ALIGN
+inline int tl_rows_ok(const tbx_tl_rows_t& r, int window, bool float4_rows) {
+  if (!r.tl_invalid || !r.attr || !r.row_invalid || r.ld_attr < 5 + window) return TBX_ERR_ARG;
+  if ((r.ld_attr % 4) || (float4_rows && (((uintptr_t)r.attr) & 15))) return TBX_ERR_ALIGN;
+  return TBX_OK;
+}
 
 constexpr int LPT = 8;  // lanes per traffic light
 
@@ -397,7 +430,23 @@ __device__ __forceinline__ void sim_light(const tbx_sim_state_t& s, const int pa
   }
 }
 
-typedef tbx_agent_prep_args_t AgentPrepArgs;  // (field order = tbx_agent_prep's parameter groups)
+typedef tbx_agent_prep_args_t AgentPrepArgs;
+
+// tbx_agent_prep's arguments (host side): the check of the stand-alone call and of the agents' step tail on *next_prep. First failure wins:
+//   1  a required pointer NULL (hist_*, ag_attr6, freqs_*, tok_*, attr, pe, row_invalid)              TBX_ERR_ARG
+//   2  n_tok <= 0, n_ag <= 0, n_tok % n_ag, window outside 1..23 (attribute row: 9 + window <= 32),
+//      pe_dim outside {64, 128}                                                                       TBX_ERR_UNSUPPORTED
+//   3  type_mask without ag_type_idx                                                                  TBX_ERR_ARG
+//   4  dest without mp_tok_pose, navi_pose3, navi_row, n_mp > 0, mp_batch_div > 0                     TBX_ERR_ARG
+inline int agent_prep_ok(const tbx_agent_prep_args_t& a) {
+  if (!a.hist_valid || !a.hist_pose || !a.hist_motion || !a.ag_attr6 || !a.freqs_xy || !a.freqs_yaw || !a.tok_pose || !a.tok_invalid ||
+      !a.attr || !a.pe || !a.row_invalid)
+    return TBX_ERR_ARG;
+  if (a.n_tok <= 0 || a.n_ag <= 0 || a.n_tok % a.n_ag != 0 || a.window <= 0 || a.window > 23 || (a.pe_dim != 64 && a.pe_dim != 128)) return TBX_ERR_UNSUPPORTED;
+  if (a.type_mask != nullptr && !a.ag_type_idx) return TBX_ERR_ARG;
+  if (a.dest != nullptr && (!a.mp_tok_pose || !a.navi_pose3 || !a.navi_row || a.n_mp <= 0 || a.mp_batch_div <= 0)) return TBX_ERR_ARG;
+  return TBX_OK;
+}
 
 // (contraction off: HIP's __fmul_rn / __fadd_rn are plain operators, and which of the two products the compiler fuses into the sum
 // is otherwise its choice per call site - the standalone kernel and the decoder layer's tail would round differently)

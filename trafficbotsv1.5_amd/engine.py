@@ -95,7 +95,7 @@ class Schedule:
     knn_main: bool = True  # the agents' K-nearest searches on the stepping stream (no cross-queue wait in front of the first attention launch); the auxiliary stream keeps the navigation embedding, joined before the LAST layer
     sim_before_join: bool = True  # the agents' tbx_sim_step on their own stream before the lights' stream is joined
     dec_tail_mfma: bool = True  # tbx_knarpe_dec_layer's LINEAR stages (folds, projections, FFN, heads) on the split-bf16 matrix path
-    pe_rides: bool = True       # tbx_knn_embed_multi_pe: the navigation pose embedding in the searches' launch
+    pe_rides: bool = True       # tbx_knn_embed_multi's pe: the navigation pose embedding in the searches' launch
     # ---- RolloutEngine
     tl_prep_rides: bool = True  # tbx_tl_prep inside the lights' tbx_sim_step launch
     lights_ahead: bool = True   # False: the sequential order on one stream (tl encoder -> agents -> tbx_sim_step)

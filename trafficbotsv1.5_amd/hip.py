@@ -47,14 +47,10 @@ def knn_embed(src_pose, src_invalid, tgt_pose, tgt_invalid, k: int, dist_limit: 
 def knn_embed_multi(jobs, freqs_xy=None, freqs_yaw=None, pe_dim: int = 128, pose_embed_job=None):
     """Several `knn_embed` searches in one launch. jobs: dicts with knn_embed's arguments (src_pose, src_invalid, tgt_pose,
     tgt_invalid, k, dist_limit, tgt_batch_div, want_rel_pose, want_emb, out) -> list of (idx, invalid, rel_pose, emb).
-    pose_embed_job = dict(pose3, freqs_xy, freqs_yaw, pe_dim, out[, col_off]): a `pose_embed` in the same launch (tbx_knn_embed_multi_pe)."""
+    pose_embed_job = dict(pose3, freqs_xy, freqs_yaw, pe_dim, out[, col_off]): a `pose_embed` in the same launch."""
     outs, cj = _knn_jobs(jobs, pe_dim)
-    if pose_embed_job is not None:
-        pj = _pose_job(pose_embed_job)
-        _check(load().tbx_knn_embed_multi_pe(cj, len(jobs), _cptr(freqs_xy), _cptr(freqs_yaw), pe_dim, C.byref(pj), stream_ptr()),
-               "tbx_knn_embed_multi_pe")
-        return outs
-    _check(load().tbx_knn_embed_multi(cj, len(jobs), _cptr(freqs_xy), _cptr(freqs_yaw), pe_dim, stream_ptr()), "tbx_knn_embed_multi")
+    pj = _pose_job(pose_embed_job) if pose_embed_job is not None else None
+    _check(load().tbx_knn_embed_multi(cj, len(jobs), _cptr(freqs_xy), _cptr(freqs_yaw), pe_dim, pj, stream_ptr()), "tbx_knn_embed_multi")
     return outs
 
 
@@ -415,7 +411,7 @@ def front(window: dict, proj: dict, rider=None, jobs=None, pose_embed_job=None):
 
 def agent_prep_args(hist_valid, hist_pose, hist_motion, ag_attr6, ag_type_idx, freqs_xy, freqs_yaw, pe_dim, out, dest=None,
                     mp_tok_pose=None, n_mp=0, mp_batch_div=1) -> AgentPrepArgs:
-    """agent_prep's arguments as tbx_agent_prep_args_t (the fused step tail of tbx_knarpe_dec_layer)."""
+    """tbx_agent_prep_args_t: what agent_prep launches on, and what the fused step tail of tbx_knarpe_dec_layer takes as next_prep."""
     n, A, W = hist_valid.shape
     a = AgentPrepArgs()
     a.hist_valid, a.hist_pose, a.hist_motion = _cptr(hist_valid, torch.uint8), _cptr(hist_pose, torch.float32), _cptr(hist_motion, torch.float32)
@@ -428,23 +424,20 @@ def agent_prep_args(hist_valid, hist_pose, hist_motion, ag_attr6, ag_type_idx, f
     return a
 
 
-def agent_prep(hist_valid, hist_pose, hist_motion, ag_attr6, ag_type_idx, freqs_xy, freqs_yaw, pe_dim, out, dest=None,
-               mp_tok_pose=None, n_mp=0, mp_batch_div=1):
-    n, A, W = hist_valid.shape
-    rc = load().tbx_agent_prep(
-        _cptr(hist_valid, torch.uint8), _cptr(hist_pose, torch.float32), _cptr(hist_motion, torch.float32),
-        _cptr(ag_attr6, torch.float32), _cptr(ag_type_idx, torch.uint8), n, A, W, _cptr(freqs_xy), _cptr(freqs_yaw), pe_dim,
-        _ptr(out["tok_pose"]), _ptr(out["tok_invalid"]), _ptr(out["attr"]), _ptr(out["pe"]), _ptr(out["row_invalid"]),
-        _ptr(out.get("type_mask")), _cptr(dest, torch.int64), _cptr(mp_tok_pose, torch.float32), n_mp, mp_batch_div,
-        _ptr(out.get("navi_pose3")), _ptr(out.get("navi_row")), stream_ptr())
-    _check(rc, "tbx_agent_prep")
+def agent_prep(*args, **kw):
+    """tbx_agent_prep (arguments: agent_prep_args)."""
+    _check(load().tbx_agent_prep(C.byref(agent_prep_args(*args, **kw)), stream_ptr()), "tbx_agent_prep")
+
+
+def _tl_rows(tl_invalid, attr, row_invalid) -> TlRows:
+    """tbx_tl_rows_t: tl_invalid u8 [n*L], attr f32 [n*L*W, ld], row_invalid u8 [n*L*W]."""
+    return TlRows(_cptr(tl_invalid, torch.uint8), _ptr(attr, torch.float32), _ptr(row_invalid, torch.uint8), attr.stride(0), 0)
 
 
 def tl_prep(hist_tl, tl_invalid, attr, row_invalid):
     n, L, W = hist_tl.shape
-    rc = load().tbx_tl_prep(_cptr(hist_tl, torch.uint8), _cptr(tl_invalid, torch.uint8), n, L, W, attr.stride(0),
-                            _ptr(attr, torch.float32), _ptr(row_invalid, torch.uint8), stream_ptr())
-    _check(rc, "tbx_tl_prep")
+    rows = _tl_rows(tl_invalid, attr, row_invalid)
+    _check(load().tbx_tl_prep(_cptr(hist_tl, torch.uint8), n, L, W, C.byref(rows), stream_ptr()), "tbx_tl_prep")
 
 
 def map_prep(mp_valid_u8, mp_type11, mp_pose, attr, pe, row_invalid, tok_pose, tok_invalid):
@@ -459,13 +452,9 @@ SIM_AGENTS, SIM_LIGHTS, SIM_ADVANCE, SIM_NO_DISABLE, SIM_NO_APPEND, SIM_APPEND =
 
 def sim_step(state: SimState, parts: int = SIM_AGENTS | SIM_LIGHTS | SIM_ADVANCE, tl_prep=None):
     """tl_prep = (tl_invalid u8 [n*L], attr f32 [n*L*W, ld], row_invalid u8 [n*L*W]): the lights' update also writes the tbx_tl_prep
-    rows of their new windows (tbx_sim_step_tl_prep)."""
+    rows of their new windows (tbx_sim_step's tl_rows)."""
     assert hip_base.DEFERRED is None, "tbx_sim_step inside a deferred step (the one-queue step runs the lights' update in their last layer's tail)"
-    if tl_prep is not None:
-        inv, attr, row_inv = tl_prep
-        _check(load().tbx_sim_step_tl_prep(C.byref(state), parts, _cptr(inv, torch.uint8), attr.stride(0), _ptr(attr, torch.float32),
-                                           _ptr(row_inv, torch.uint8), stream_ptr()), "tbx_sim_step_tl_prep")
-        return
-    _check(load().tbx_sim_step_parts(C.byref(state), parts, stream_ptr()), "tbx_sim_step_parts")
+    rows = _tl_rows(*tl_prep) if tl_prep is not None else None
+    _check(load().tbx_sim_step(C.byref(state), parts, rows, stream_ptr()), "tbx_sim_step")
 
 

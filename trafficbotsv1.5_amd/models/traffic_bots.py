@@ -119,7 +119,7 @@ class TrafficBots(nn.Module):
                      prep_ready: bool = False) -> None:
         """The agent half (traffic_bots.py:200-221): agent tokens attending to agents / map / tl K/V tables `tl_kv`, then
         navi + latent + action head -> out['action_mean'].
-        fused_tail = dict(sim_state, parts): the rollout engine's request to run the agents' tbx_sim_step_parts and the NEXT step's
+        fused_tail = dict(sim_state, parts): the rollout engine's request to run the agents' part of tbx_sim_step and the NEXT step's
         tbx_agent_prep in the tail of the launch that produces the actions (tbx_heads_tail_t.sim_state / next_prep); whether it
         happened is reported in out["prep"]["_tail_fused"]. prep_ready: this step's tbx_agent_prep already ran (that tail)."""
         n, A, W = hist_valid.shape

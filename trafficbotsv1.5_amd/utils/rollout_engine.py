@@ -508,7 +508,7 @@ class RolloutEngine:
             assert not self.stepwise
         self.side.wait_stream(main)
         with torch.cuda.stream(self.side):
-            # logits of the previous tl encoder pass -> lights of this step (+ the one-hot rows of their new windows: tbx_sim_step_tl_prep)
+            # logits of the previous tl encoder pass -> lights of this step (+ the one-hot rows of their new windows: tbx_sim_step's tl_rows)
             if self.sched.tl_prep_rides:
                 if self._tl_prep is None:
                     hist = self.S["hist_tl"]
