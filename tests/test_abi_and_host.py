@@ -185,6 +185,24 @@ def test_new_entry_points_validate_arguments_without_a_gpu(hip):
     assert lib.tbx_train_chain_bwd(C.byref(args), None, 8, 8, None, None, None) == -1
 
 
+def test_knn_inverse_validates_its_arguments_without_a_gpu(hip):
+    """tbx_knn_inverse calls that must be refused BEFORE any launch (placeholder device addresses, never dereferenced)."""
+    lib = hip.load()
+    ARG, UNSUPPORTED = -1, -2
+    dp = lambda i: 0x10000 * (i + 1)
+
+    def f(n_batch=6, n_src=7, k=9, n_tgt=16, div=3, idx=dp(0), invalid=dp(1), ptr=dp(2), lst=dp(3)):
+        return lib.tbx_knn_inverse(idx, invalid, n_batch, n_src, k, n_tgt, div, ptr, lst, None)
+
+    assert f(n_tgt=2049) == UNSUPPORTED                       # one workgroup scans a table's counts in LDS: n_tgt <= 2048
+    assert f(n_batch=7) == ARG and f(n_batch=2) == ARG        # n_batch % tgt_batch_div != 0
+    assert f(n_batch=7, n_tgt=2049) == ARG                    # (precedence: the arguments before the shape)
+    assert f(n_batch=3 << 20, n_src=64, k=128) == UNSUPPORTED  # pair ids are 32-bit
+    for bad in (dict(idx=None), dict(invalid=None), dict(ptr=None), dict(lst=None), dict(n_batch=0), dict(n_src=0), dict(k=0), dict(n_tgt=0),
+                dict(div=0)):
+        assert f(**bad) == ARG, bad
+
+
 def test_attention_entry_points_validate_their_argument_struct_without_a_gpu(hip):
     """tbx_knarpe_attn_fwd / _fwd_mfma / _bwd on tbx_attn_t structs that must be refused BEFORE any launch (placeholder device
     addresses, never dereferenced), with the codes the positional entry points gave for the same arguments: the checks of the query

@@ -8,6 +8,7 @@ import torch
 
 from oracle import hptr_ops as H
 from oracle import trafficbots_oracle as O
+from test_hip_attn_backward import reference as attn_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -337,23 +338,8 @@ def test_attention_probability_dropout_vs_explicit_mask(tb):
     keep = hip.dropout_keep_mask(int(seed[0]), call, rows, K1 + K2, p).float()  # [rows, 4, K]
     assert 0.6 < float(keep.mean()) < 0.9
 
-    def reference(qbuf, bias_k, kv1, kv2):
-        q, qt = qbuf[:, :128].view(rows, 4, 32), qbuf[:, 128:].view(rows, 4, 128)
-        ks, vs, es, ms = [], [], [], []
-        for kv, ix, iv, e, T in ((kv1, idx[0], inv[0], emb[0], T1), (kv2, idx[1], inv[1], emb[1], T2)):
-            flat = (torch.arange(n)[:, None, None] * T + ix).reshape(rows, -1)
-            ks.append(kv[flat][..., :128].view(rows, -1, 4, 32))
-            vs.append(kv[flat][..., 128:].view(rows, -1, 4, 32))
-            es.append(e.reshape(rows, -1, 128))
-            ms.append(iv.reshape(rows, -1))
-        k, v, e, m = torch.cat(ks, 1), torch.cat(vs, 1), torch.cat(es, 1), torch.cat(ms, 1)
-        sc = (torch.einsum("rhc,rthc->rht", q, k) + torch.einsum("rhc,rtc->rht", qt, e)
-              + torch.einsum("rhc,hc->rh", q, bias_k.view(4, 32)).unsqueeze(-1)) / 32 ** 0.5
-        dead = m.all(-1)
-        sc = sc.masked_fill((m & ~dead[:, None]).unsqueeze(1), float("-inf"))
-        a = torch.softmax(sc, -1) * keep / (1 - p)
-        out = torch.cat([torch.einsum("rht,rthc->rhc", a, v).reshape(rows, 128), torch.einsum("rht,rtc->rhc", a, e).reshape(rows, 512)], 1)
-        return out.masked_fill(dead[:, None], 0.0), dead
+    def reference(qbuf, bias_k, kv1, kv2):  # the float64 evaluation shared with tests/test_hip_attn_backward.py
+        return attn_reference(qbuf, bias_k, [kv1, kv2], idx, inv, emb, (T1, T2), (1, 1), n, S, keep=keep, p=p)
 
     leaves_c = [t.clone().requires_grad_(True) for t in (qbuf, bias_k, *kvs)]
     out_c, dead = reference(*leaves_c)
