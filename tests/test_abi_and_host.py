@@ -44,6 +44,47 @@ def test_argument_validation_returns_codes_without_a_gpu(hip):
         hip.pose_embed(torch.zeros(4, 3), torch.zeros(32), torch.zeros(64), 128)  # CPU tensor: no fallback path
 
 
+def test_rowchain_refuses_before_launch(hip):
+    """check_stage / rowchain_launch of csrc/rowchain.hip return these codes before anything is launched (no GPU here; the pointers are
+    never read). ARG = -1, UNSUPPORTED = -2, ALIGN = -3."""
+    lib, S = hip.load(), hip.Stage
+    P, Q, M = 0x10000, 0x20000, 0x30000  # 16-byte aligned stand-ins for device pointers
+
+    def ex(st, n_rows=16, group_rows=0, tile=16, ldw0=132, ldw1=132, aux=260):
+        return lib.tbx_rowchain_ex((S * len(st))(*st), len(st), n_rows, group_rows, tile, ldw0, ldw1, aux, None)
+
+    def live(st, rows=4):
+        return lib.tbx_rowchain_live((S * len(st))(*st), len(st), 16, rows, 132, 132, 260, None)
+
+    load2 = dict(op=hip.OP_LOAD, dst=hip.BUF1, n=128, ld=128, src=hip.AUX, src_col=4, reserved=64, ld2=64, p0=P, p2=Q)
+    assert ex([S(flags=hip.F_LOAD2, **{**load2, "p0": P + 4})]) == -3                          # LOAD2, misaligned pointer
+    assert ex([S(flags=hip.F_LOAD2, **{**load2, "p2": Q + 8})]) == -3
+    assert ex([S(flags=hip.F_LOAD2 | hip.F_ACCUM, **load2)]) == -1                             # LOAD2 with ACCUM
+    lin = dict(op=hip.OP_LINEAR, src=hip.BUF0, dst=hip.BUF1, k=64, n=64, ld=64, p0=P)
+    assert ex([S(flags=hip.F_WPACK | hip.F_ROWZERO, **lin)]) == -1                             # ROWZERO without ROWSKIP
+    assert ex([S(flags=hip.F_WPACK | hip.F_ROWSKIP, **lin)]) == -2                             # ROWSKIP without its mask
+    assert ex([S(op=hip.OP_STORE, src=hip.BUF0, n=4, ld=8, p0=P, p1=M, reserved=2, div=4, k=16,
+                 flags=hip.F_MASKED_SUM | hip.F_OUT_BF16)]) == -2                              # MASKED_SUM into bfloat16
+    assert ex([S(op=hip.OP_POOLMAX, src=hip.BUF0, dst=hip.BUF0, n=16, k=32, ld=16, p0=P, flags=hip.F_POOL_KEEP)]) == -1  # POOL_KEEP, dst == src
+    assert ex([S(op=hip.OP_LAYERNORM, src=hip.BUF0, dst=hip.BUF0, n=516, p0=P, p1=Q)], ldw0=520, ldw1=520) == -2  # LAYERNORM wider than 512
+    assert ex([S(flags=hip.F_WPACK, **{**lin, "dst": hip.BUF0, "dst_col": 48})]) == -2         # in place, columns overlap (k = 64)
+    assert ex([S(flags=hip.F_WPACK, **{**lin, "dst": hip.BUF0, "k": 20, "dst_col": 16})]) == -2  # ... with the source's pad columns [20, 32)
+    assert ex([S(flags=hip.F_WPACK, reserved=2, div=(16 << 16) | 24, **{**lin, "n": 20, "k": 16})]) == -2  # grouped, n % 16 != 0
+    gemv = dict(lin, flags=hip.F_WGEMV)
+    assert live([S(**gemv), S(op=hip.OP_GROUPMAX, src=hip.BUF1, dst=hip.BUF1, dst_col=64, n=64)]) == -2
+    assert live([S(**gemv), S(op=hip.OP_POOLMAX, src=hip.BUF1, n=64, ld=64, p0=Q)]) == -2
+    assert live([S(**gemv), S(op=hip.OP_DROPOUT, dst=hip.BUF1, n=64, p0=M, f0=1.0)]) == -2
+    assert live([S(flags=hip.F_WPACK, **lin)]) == -2                                           # a LINEAR of a live program must be WGEMV
+    assert live([S(**lin)]) == -2
+    assert ex([S(**gemv)]) == -2                                                               # ... and only of a live program
+    assert live([S(**gemv)], rows=3) == -2
+    copy = [S(op=hip.OP_COPY, src=hip.BUF0, dst=hip.BUF1, n=4)]
+    assert ex(copy, n_rows=40, group_rows=20, tile=16) == -2                                   # group_rows > tile_rows
+    assert ex(copy, n_rows=40, group_rows=11, tile=16) == -1                                   # n_rows % group_rows != 0
+    assert ex(copy, tile=48, ldw0=400, ldw1=400) == -2                                         # (400 + 400 + 260) * 48 * 4 B > 160 KiB
+    assert ex(copy, tile=16, ldw0=1028, ldw1=1028, aux=512) == -2                              # (1028 + 1028 + 512) * 16 * 4 B > 160 KiB
+
+
 def test_state_dict_layout_equals_reference(tb, golden_dir):
     M = import_module("trafficbots_amd.models.traffic_bots")
     model = M.TrafficBots(**tb.config.default_model_cfg())

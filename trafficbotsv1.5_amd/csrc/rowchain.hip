@@ -837,12 +837,14 @@ __device__ void op_groupmax(const tbx_stage_t& s, const Tile<MT, EXT>& t) {
   // p1 != NULL: the masked form - one stage for [ROWMASK(-inf) -> GROUPMAX -> ROWMASK(0) over both halves] of a PointNet layer
   // (polyline_encoder.py:52-58): rows whose byte p1[g] is set (and padding rows) are left out of the maximum and come out as 0 in
   // src and dst columns alike. The tile's row bytes are read once per wave (one ballot), not once per row and thread.
+  // p1 == NULL: only the padding rows of a tile that is not full are left out - a group narrower than its tile, or a last
+  // tile with fewer groups, must not see the rows beyond it (LOAD leaves them 0: above a maximum of negative features).
   const uint8_t* mask = (const uint8_t*)s.p1;
   unsigned long long inv = 0ull;
-  if (mask != nullptr) {
+  if (mask != nullptr || t.n_valid < ROWS) {
     const int lane = threadIdx.x & 63;
     bool m = true;
-    if (lane < ROWS && lane < t.n_valid) m = gld1(mask + t.g0 + lane) != 0;
+    if (lane < ROWS && lane < t.n_valid) m = mask != nullptr && gld1(mask + t.g0 + lane) != 0;
     inv = __ballot(m);
   }
   auto off = [&](int r) { return ((inv >> r) & 1ull) != 0ull; };

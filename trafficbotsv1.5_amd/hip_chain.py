@@ -155,7 +155,8 @@ class Chain:
         return self._add(op=OP_ROWMASK, dst=dst, dst_col=dst_col, n=n, f0=fill, flags=flags, div=div, p0=mask)
 
     def groupmax(self, src, src_col, dst, dst_col, n, mask=None):
-        """mask u8 [rows]: masked rows stay out of the maximum and are zeroed in the src and dst columns (see include/tbx_hip.h)."""
+        """mask u8 [rows]: masked rows stay out of the maximum and are zeroed in the src and dst columns (see include/tbx_hip.h);
+        a tile's padding rows never take part, with or without a mask."""
         return self._add(op=OP_GROUPMAX, src=src, dst=dst, src_col=src_col, dst_col=dst_col, n=n, p1=mask)
 
     def poolmax(self, src, src_col, n, out, out_col=0, mask=None, keep=None):
