@@ -1060,4 +1060,10 @@ int tbx_pose_to_global(const float* xy, int ld_xy, const float* yaw, int ld_yaw,
 #ifdef __cplusplus
 }
 #endif
+
+/* Entry points added after ABI 7 was laid down, without a change to any declaration above, are declared in extension headers that
+ * this header includes - including tbx_hip.h declares everything libtbx_hip.so exports. tbx_version() stays 7: a host built against
+ * the declarations above runs unchanged on a library that has the extensions. */
+#include "tbx_hip_metrics.h" /* tbx_rollout_metrics */
+
 #endif /* TBX_HIP_H */

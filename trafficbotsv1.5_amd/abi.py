@@ -12,6 +12,7 @@ _lib = None
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "csrc" / "libtbx_hip.so"
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
+EXTENSION_HEADER_PATHS = (HEADER_PATH.parent / "tbx_hip_metrics.h",)  # included by tbx_hip.h: entry points added after ABI 7 was laid down
 
 # ---- constants mirrored from include/tbx_hip.h
 OP_LOAD, OP_LINEAR, OP_LAYERNORM, OP_ADD, OP_COPY, OP_ROWMASK, OP_GROUPMAX, OP_POOLMAX, OP_STORE, OP_CLAMP, OP_DROPOUT = range(1, 12)
@@ -202,14 +203,28 @@ class RuleCtx(C.Structure):
 
 
 RULE_COLLIDED, RULE_COLLIDED_WOSAC, RULE_RUN_ROAD_EDGE, RULE_RUN_RED_LIGHT, RULE_PASSIVE = 1, 2, 4, 8, 16
+METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
 
 _lib = None
+
+
+_DECL = r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\("
 
 
 def declared_symbols() -> List[str]:
     """Entry points declared in include/tbx_hip.h (the C-ABI contract)."""
     txt = HEADER_PATH.read_text()
-    return sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\(", txt, flags=re.M)))
+    return sorted(set(re.findall(_DECL, txt, flags=re.M)))
+
+
+def extension_symbols() -> List[str]:
+    """Entry points declared in the extension headers include/tbx_hip.h includes (tbx_rollout_metrics): with declared_symbols(),
+    everything the library exports."""
+    included = set(re.findall(r'^#include "(tbx_\w+\.h)"', HEADER_PATH.read_text(), flags=re.M))
+    missing = [p.name for p in EXTENSION_HEADER_PATHS if p.name not in included]
+    if missing:
+        raise ImportError(f"include/tbx_hip.h does not include {missing}")
+    return sorted({s for p in EXTENSION_HEADER_PATHS for s in re.findall(_DECL, p.read_text(), flags=re.M)})
 
 
 def load():
@@ -223,7 +238,7 @@ def load():
             f"{lib_path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no fallback path.")
     lib = C.CDLL(str(lib_path))
-    for s in declared_symbols():
+    for s in declared_symbols() + extension_symbols():
         if not hasattr(lib, s):
             raise ImportError(f"libtbx_hip.so does not export {s}")
     lib.tbx_error_string.restype = C.c_char_p
@@ -303,14 +318,15 @@ def load():
     lib.tbx_attn_fold_fwd.argtypes = [vp] * 14
     lib.tbx_attn_fold_bwd.argtypes = [vp] * 19
     lib.tbx_rule_navi_check.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.tbx_rollout_metrics.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     for name in ("tbx_layer_tile", "tbx_heads_tile", "tbx_window_tile", "tbx_front", "tbx_tall_linear", "tbx_pack_weight_mfma32", "tbx_pack_weight_mfma32_multi", "tbx_pack_weight", "tbx_pack_weight_split", "tbx_pack_weight_gemv", "tbx_rowchain_live", "tbx_knarpe_dec_mid", "tbx_knarpe_dec_layer", "tbx_knn_embed_multi", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd", "tbx_knarpe_attn_bwd", "tbx_keyed_dropout", "tbx_linear_wgrad_splits", "tbx_linear_wgrad", "tbx_linear_wgrad_bf16", "tbx_tall_linear_bf16", "tbx_tl_tail_tile", "tbx_tl_tail_tile_bf16", "tbx_layernorm_fwd", "tbx_layernorm_bwd_partials", "tbx_layernorm_bwd", "tbx_layernorm_bwd_add", "tbx_residual_drop_fwd", "tbx_residual_drop_bwd", "tbx_relu_drop_fwd", "tbx_relu_drop_bwd", "tbx_pair_bias_relu", "tbx_pointnet_tail_fwd", "tbx_pointnet_tail_bwd", "tbx_masked_maxpool_fwd", "tbx_masked_maxpool_bwd", "tbx_train_chain_fwd", "tbx_train_chain_fwd_windows", "tbx_train_chain_bwd", "tbx_knn_inverse", "tbx_rowchain", "tbx_rowchain_ex", "tbx_agent_prep", "tbx_tl_prep",
                  "tbx_map_prep", "tbx_sim_step", "tbx_rule_tables", "tbx_rule_grid", "tbx_rule_grid_cells", "tbx_rule_check", "tbx_rule_accumulate", "tbx_filter_futures", "tbx_rule_navi_check", "tbx_attn_fold_fwd", "tbx_attn_fold_bwd", "tbx_front_pair", "tbx_knarpe_dec_layer_pair",
-                 "tbx_womd_modes", "tbx_pose_to_global", "tbx_rel_pose_dense", "tbx_diffbar_reward", "tbx_knarpe_attn_fwd_mfma"):
+                 "tbx_womd_modes", "tbx_pose_to_global", "tbx_rel_pose_dense", "tbx_diffbar_reward", "tbx_knarpe_attn_fwd_mfma", "tbx_rollout_metrics"):
         getattr(lib, name).restype = C.c_int
     if lib.tbx_version() != 7:
         raise ImportError("libtbx_hip.so ABI version mismatch")
     # (an entry point without argtypes would get 64-bit handles - stream pointers under graph capture - as C ints)
-    untyped = [s for s in declared_symbols() if getattr(lib, s).argtypes is None and s not in ("tbx_error_string", "tbx_version")]
+    untyped = [s for s in declared_symbols() + extension_symbols() if getattr(lib, s).argtypes is None and s not in ("tbx_error_string", "tbx_version")]
     if untyped:
         raise ImportError(f"abi.load(): no argtypes for {untyped}")
     _lib = lib

@@ -1,5 +1,5 @@
 """ctypes wrappers of the rule-check / rollout-filter / post-processing entry points (tbx_rule_*, tbx_filter_futures, tbx_womd_modes,
-tbx_pose_to_global). Re-exported by hip.py."""
+tbx_pose_to_global, tbx_rollout_metrics). Re-exported by hip.py."""
 import ctypes as C
 import os
 from typing import List, Optional, Sequence
@@ -150,3 +150,40 @@ def pose_to_global(xy, ld_xy: int, yaw, ld_yaw: int, scenario_center, scenario_y
                                    stream_ptr())
     _check(rc, "tbx_pose_to_global")
     return pos, out_yaw
+
+
+def u8_row_steps(t, tail: int = 0) -> Optional[int]:
+    """t [R, A, T] (+ `tail` dense trailing dimensions): rows of a log or a time slice of one -> the steps per row of the underlying
+    log (what log_row_steps finds for the float logs), else None. Dimensions of size 1 carry no stride information."""
+    shape, stride = t.shape, t.stride()
+    inner = 1
+    for d in range(t.dim() - 1, t.dim() - 1 - tail, -1):
+        if shape[d] > 1 and stride[d] != inner:
+            return None
+        inner *= shape[d]
+    R, A, T = shape[:3]
+    if T > 1 and stride[2] != inner:
+        return None
+    ld = stride[1] if A > 1 else (stride[0] if R > 1 else T * inner)
+    if ld % inner or ld // inner < T or (R > 1 and stride[0] != A * ld):
+        return None
+    return ld // inner
+
+
+def rollout_metrics(acc, partials, pred_valid, n_k: int, ld_t: int, t0: int, n_t: int, pred_pose=None, pred_motion=None, gt_valid=None,
+                    gt_pose=None, gt_motion=None, gt_t0: int = 0, flags=None, ld_flags: int = 0, outside_map=None, dest_reached=None,
+                    goal_reached=None, ag_type=None):
+    """tbx_rollout_metrics: the 13 sums of ErrorMetrics / TrafficRuleMetrics of a rollout log added into acc [METRICS_SLOTS] f64.
+    pred_valid [R, A, ..] u8 and the other logs are given as tensors whose data pointers address (row 0, agent 0, step 0) of rows
+    ld_t steps long - views are fine, only the pointers cross; the ground truth and ag_type are dense. partials
+    [METRICS_PARTIAL_ROWS, METRICS_SLOTS] f64 workspace."""
+    R, A = pred_valid.shape[:2]
+    if acc.numel() < METRICS_SLOTS or partials.numel() < METRICS_PARTIAL_ROWS * METRICS_SLOTS:
+        raise RuntimeError("rollout_metrics: acc needs METRICS_SLOTS, partials METRICS_PARTIAL_ROWS * METRICS_SLOTS float64 values")
+    u8, f32 = torch.uint8, torch.float32
+    rc = load().tbx_rollout_metrics(_ptr(pred_valid, u8), _ptr(pred_pose, f32), _ptr(pred_motion, f32), R, n_k, A, ld_t, t0, n_t,
+                                    _cptr(gt_valid, u8), _cptr(gt_pose, f32), _cptr(gt_motion, f32),
+                                    gt_valid.shape[-1] if gt_valid is not None else 0, gt_t0, _ptr(flags, u8), ld_flags,
+                                    _ptr(outside_map, u8), _ptr(dest_reached, u8), _ptr(goal_reached, u8), _cptr(ag_type, u8),
+                                    _cptr(acc, torch.float64), _cptr(partials, torch.float64), stream_ptr())
+    _check(rc, "tbx_rollout_metrics")

@@ -4,8 +4,11 @@
 The rollout is a device-resident state machine (utils/rollout_engine.py) replaying one hipGraph per step; scenes and
 rollouts are independent, so multi-GPU inference shards them over ranks with no collective.
 `womd_post_processing` / `wosac_post_processing` (data_modules/) turn the rollout log into scored modes and global-frame records on the
-device; WOMD / WOSAC metrics, submission writers and video logging of the reference are out of scope.
+device; `validation_step` / `validation_epoch_end` run the reference's statements around them and reduce the rollout logs to the
+epoch's `val/loss`, error and traffic-rule numbers on the device (models/metrics/logging.py: tbx_rollout_metrics). WOMD / WOSAC
+metrics, submission writers and video logging of the reference are out of scope.
 """
+import copy
 import dataclasses
 from collections import OrderedDict
 from typing import Dict, Optional
@@ -21,6 +24,8 @@ from ..data_modules.scene_centric import SceneCentricPreProcessing
 from ..data_modules.womd_post_processing import WOMDPostProcessing
 from ..data_modules.wosac_post_processing import WOSACPostProcessing
 from ..hip_base import weights_stamp
+from ..models.metrics.logging import ErrorMetrics, TrafficRuleMetrics
+from ..models.metrics.training import TrainingMetrics
 from ..models.modules.distributions import MyDist
 from ..models.traffic_bots import TrafficBots
 from ..utils.buffer import RolloutBuffer
@@ -100,6 +105,13 @@ class WaymoMotion(LightningModule):
         self.teacher_forcing_training = TeacherForcing(**teacher_forcing_training)
         self.teacher_forcing_reactive_replay = TeacherForcing(**teacher_forcing_reactive_replay)
         self.teacher_forcing_joint_future_pred = TeacherForcing(**teacher_forcing_joint_future_pred)
+        # validation (waymo_motion.py:83,92-98,106): reactive_replay is scored like training plus errors and rule rates, joint_future_pred
+        # by its rule rates
+        train_navi, train_latent = not self.model.navi_encoder.dummy, not self.model.latent_encoder.dummy
+        self.train_metrics_reactive_replay = TrainingMetrics("reactive_replay", train_navi, train_latent, **training_metrics)
+        self.err_metrics_reactive_replay = ErrorMetrics("reactive_replay")
+        self.rule_metrics_reactive_replay = TrafficRuleMetrics("reactive_replay")
+        self.rule_metrics_joint_future_pred = TrafficRuleMetrics("joint_future_pred")
         # waymo_motion.py:99-110; a configuration without these sections builds neither module
         if womd_post_processing:
             self.womd_post_processing = WOMDPostProcessing(step_gt=time_step_gt, step_current=time_step_current,
@@ -386,6 +398,85 @@ class WaymoMotion(LightningModule):
             self.log(f"training/{k}", v, on_step=True)
         self.last_metrics = out
         return out["loss"]
+
+    # ------------------------------------------------------------------ validation
+    @staticmethod
+    def _without_joint_future_axis(buffer: RolloutBuffer) -> RolloutBuffer:
+        """What the reference's TrainingMetrics.update reads of a reactive_replay buffer (`.squeeze(1)` of pred_valid, the teacher-forcing
+        mask and the rewards, models/metrics/training.py:91,102,124-125): views, in a shallow copy - the caller's buffer keeps its axis."""
+        out = copy.copy(buffer)
+        out.pred_valid, out.mask_teacher_forcing = buffer.pred_valid.squeeze(1), buffer.mask_teacher_forcing.squeeze(1)
+        out.diffbar_reward = {k: v.squeeze(1) for k, v in buffer.diffbar_reward.items()}
+        return out
+
+    @torch.no_grad()
+    def validation_step(self, batch: Dict[str, Tensor], batch_idx: int) -> None:
+        """waymo_motion.py:526-608 statement by statement, then :610-613, :629-633 and :649 where the configuration has the
+        post-processing sections (results on `last_womd_reactive_replay`, `last_womd_joint_future_pred`, `last_wosac_data`). The metric
+        updates are reductions of the device-resident logs into device-resident states: nothing here waits for the device. The
+        caller's `batch` dict is left as it is (the scene-centric keys go into a copy). WOMD / WOSAC metrics, the submission
+        writers and log_val_video are not part of this package."""
+        with engine.use(self.schedule):
+            batch = self.pre_processing(dict(batch))
+            model = self.model
+            mp_tokens = model.mp_encoder(batch["sc/mp_valid"], batch["sc/mp_attr"], batch["sc/mp_pose"], batch["ref/mp_type"])
+            tl_tokens = model.tl_encoder.pre_compute(tl_valid=batch["gt/tl_valid"], tl_attr=batch["sc/tl_attr"], tl_pose=batch["sc/tl_pose"],
+                                                     **mp_tokens)
+            latent_post = model.latent_encoder(ag_valid=batch["gt/ag_valid"], ag_attr=batch["sc/ag_attr"], ag_motion=batch["gt/ag_motion"],
+                                               ag_pose=batch["gt/ag_pose"], ag_type=batch["ref/ag_type"], tl_state=batch["gt/tl_state"],
+                                               mp_tokens=mp_tokens, tl_tokens=tl_tokens, posterior=True)
+            latent_prior = model.latent_encoder(ag_valid=batch["sc/ag_valid"], ag_attr=batch["sc/ag_attr"], ag_motion=batch["sc/ag_motion"],
+                                                ag_pose=batch["sc/ag_pose"], ag_type=batch["ref/ag_type"], tl_state=batch["sc/tl_state"],
+                                                mp_tokens=mp_tokens, tl_tokens=tl_tokens, posterior=False)
+            navi_pred = model.navi_predictor(ag_valid=batch["sc/ag_valid"], ag_attr=batch["sc/ag_attr"], ag_motion=batch["sc/ag_motion"],
+                                             ag_pose=batch["sc/ag_pose"], ag_type=batch["ref/ag_type"], **mp_tokens)
+            ag_latent = None if latent_post is None else latent_post.sample(deterministic=True)
+            ag_latent_valid = None if latent_post is None else latent_post.valid
+            buffer_reactive_replay = self.reactive_replay(batch=batch, mp_tokens=mp_tokens, tl_tokens=tl_tokens, ag_latent=ag_latent,
+                                                          ag_latent_valid=ag_latent_valid, ag_navi=batch["gt/ag_navi"],
+                                                          ag_navi_valid=batch["gt/ag_valid"].any(-1),
+                                                          teacher_forcing=self.teacher_forcing_reactive_replay, deterministic_action=True)
+            # before joint_future_pred, which repeats the prior latent and the destination distribution in place (:583)
+            self.train_metrics_reactive_replay.update(buffer=self._without_joint_future_axis(buffer_reactive_replay), ag_role=batch["ref/ag_role"],
+                                                      navi_pred=navi_pred, navi_gt=batch["gt/ag_navi"], latent_post=latent_post,
+                                                      latent_prior=latent_prior)
+            buffer_joint_future_pred = self.joint_future_pred(batch=batch, mp_tokens=mp_tokens, tl_tokens=tl_tokens, ag_latent_dist=latent_prior,
+                                                              ag_navi_dist=navi_pred, teacher_forcing=self.teacher_forcing_joint_future_pred,
+                                                              n_joint_future=self.hparams.n_joint_future_wosac)
+            self.err_metrics_reactive_replay.update(buffer_reactive_replay, batch["gt/ag_valid"], batch["gt/ag_pose"], batch["gt/ag_motion"])
+            self.rule_metrics_reactive_replay.update(buffer_reactive_replay, batch["ref/ag_type"])
+            self.rule_metrics_joint_future_pred.update(buffer_joint_future_pred, batch["ref/ag_type"])
+            if hasattr(self, "womd_post_processing"):
+                self.last_womd_reactive_replay = self.womd_post_processing(
+                    ag_type=batch["ref/ag_type"], trajs=buffer_reactive_replay.pred_pose[:, :, :, buffer_reactive_replay.step_future_start:])
+                self.last_womd_joint_future_pred = self.womd_post_processing(
+                    ag_type=batch["ref/ag_type"], trajs=buffer_joint_future_pred.pred_pose[:, :, :, buffer_joint_future_pred.step_future_start:],
+                    scores=buffer_joint_future_pred.log_prob)
+            if hasattr(self, "wosac_post_processing"):
+                self.last_wosac_data = self.wosac_post_processing(batch, buffer_joint_future_pred)
+        return None
+
+    def validation_epoch_end(self, outputs) -> None:
+        """waymo_motion.py:673-715 without the WOMD / WOSAC parts: the states summed over the ranks where torch.distributed runs (the
+        reference's dist_reduce_fx="sum"), then compute / log / reset per metric and `val/loss`, the checkpoint callback's monitor."""
+        tm = self.train_metrics_reactive_replay
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            flat = torch.stack([getattr(tm, n) for n in tm._names])
+            torch.distributed.all_reduce(flat, op=torch.distributed.ReduceOp.SUM)
+            for n, v in zip(tm._names, flat):
+                getattr(tm, n).copy_(v)
+        self.log("epoch", self.current_epoch, on_epoch=True)
+        epoch_train_metrics_reactive_replay = None
+        for m in (tm, self.err_metrics_reactive_replay, self.rule_metrics_reactive_replay, self.rule_metrics_joint_future_pred):
+            if m is not tm:
+                m.sync()
+            out = m.compute()
+            if m is tm:
+                epoch_train_metrics_reactive_replay = out
+            for k, v in out.items():
+                self.log(k, v, on_epoch=True)
+            m.reset()
+        self.log("val/loss", epoch_train_metrics_reactive_replay["reactive_replay/loss"], on_epoch=True)
 
     def configure_optimizers(self):
         """waymo_motion.py:820-838: AdamW, separate lr group for navi_predictor, StepLR."""
