@@ -1065,5 +1065,7 @@ int tbx_pose_to_global(const float* xy, int ld_xy, const float* yaw, int ld_yaw,
  * this header includes - including tbx_hip.h declares everything libtbx_hip.so exports. tbx_version() stays 7: a host built against
  * the declarations above runs unchanged on a library that has the extensions. */
 #include "tbx_hip_metrics.h" /* tbx_rollout_metrics */
+/* ... and the entry points of libtbx_hip_reward.so, a library of its own built beside this one (libtbx_hip.so exports none of them): */
+#include "tbx_hip_reward.h"  /* tbx_collision_reward_fwd / _bwd, tbx_train_chain_bwd_pose */
 
 #endif /* TBX_HIP_H */

@@ -1,0 +1,133 @@
+"""CPU checks of the collision term of the differentiable reward (w_collision > 0): the float64 restatement the GPU tests compare
+against (tests/collision_ref.py) reproduces the REFERENCE's recorded outputs (tests/golden/collision_reward.npz, made by
+tests/golden/make_golden_collision.py), and the switch is accepted where it used to be refused.
+
+Tolerances: 8 x the reference's own float32 - float64 difference (bound_c on the term, bound_g on the gradient; recorded in the
+fixture) + 1e-7 / 1e-6. The gradient is compared on the agents whose discrete decisions (arg-max partner, arg-min circle pair, clamp)
+are not within rounding of flipping - the fixture records the margins, collision_ref.inside_margins applies the floors."""
+import sys
+from importlib import import_module
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import collision_ref as CR  # noqa: E402
+
+CASES = ["s3_a5_w8", "s2_a64_w60", "s2_a65_w40", "s4_a33_w25", "s2_a128_w120", "s1_a1_w1"]
+
+
+@pytest.fixture(scope="module")
+def golden(golden_dir):
+    return np.load(golden_dir / "collision_reward.npz")
+
+
+def case_inputs(g, name):
+    return {k: torch.from_numpy(g[f"{name}/{k}"]) for k in ("pred_valid", "pred_pose", "pred_motion", "gt_valid", "gt_pose", "gt_motion", "ag_size")}
+
+
+def test_fixture_inputs_are_the_seeded_generator_s(tb, golden):
+    for name in CASES:
+        n_sc, A, spread = (int(x[1:]) for x in name.split("_"))
+        c = tb.synthetic.make_collision_case(n_sc, A, 1, float(spread))
+        for k, v in case_inputs(golden, name).items():
+            assert torch.equal(c[k], v), (name, k)
+
+
+@pytest.mark.parametrize("mode", ["max", "sum"])
+@pytest.mark.parametrize("name", CASES)
+def test_restatement_reproduces_the_reference(golden, name, mode):
+    c = case_inputs(golden, name)
+    bound_c, bound_g = float(golden["bound_c"]), float(golden["bound_g"])
+    term = CR.term(c["pred_valid"], c["pred_pose"], c["ag_size"], mode == "max")
+    ref = torch.from_numpy(golden[f"{name}/{mode}/term"])
+    d_c = float((term - ref).abs().max())
+    grad = CR.grad(c["pred_valid"], c["pred_pose"], c["ag_size"], mode == "max")
+    m = {k: torch.from_numpy(golden[f"{name}/{mode}/margin_{k}"]) for k in CR.MARGIN_FLOOR}
+    keep = CR.inside_margins(m)
+    assert int((~keep).sum()) <= 0.05 * keep.numel()
+    d_g = float(((grad - torch.from_numpy(golden[f"{name}/{mode}/grad"])).abs() * keep[..., None]).max())
+    print(f"[restatement vs reference, {name}, {mode}] term max |d| {d_c:.3g} (bound {8 * bound_c + 1e-7:.3g}), gradient max |d| {d_g:.3g} "
+          f"(bound {8 * bound_g + 1e-6:.3g}), {int((~keep).sum())} agents outside the margins")
+    assert d_c <= 8 * bound_c + 1e-7
+    assert d_g <= 8 * bound_g + 1e-6 and bool(torch.isfinite(grad).all())
+    # the recorded margins are this module's
+    for k, v in CR.margins(c["pred_valid"], c["pred_pose"], c["ag_size"], mode == "max").items():
+        assert torch.equal(v, m[k]), k
+
+
+@pytest.mark.parametrize("il", [True, False])
+@pytest.mark.parametrize("mode", ["max", "sum"])
+def test_restated_get_reproduces_the_reference(golden, mode, il):
+    bound_c = float(golden["bound_c"])
+    for name in CASES:
+        c = case_inputs(golden, name)
+        got = CR.get(float(golden["w_collision"]), mode == "max", il, 1e-1, 1e1, 1e-1, **c)
+        for k, v in got.items():
+            ref = torch.from_numpy(golden[f"{name}/{mode}/get_il{int(il)}/{k}"])
+            if v.dtype == torch.bool:
+                assert torch.equal(v, ref), (name, k)
+            else:
+                assert float((v - ref).abs().max()) <= 8 * bound_c + 1e-7, (name, k)
+
+
+def test_no_valid_agent_gives_zero_not_nan():
+    """The stated deviation: the reference divides 0 by 0 in sum mode."""
+    valid = torch.zeros(1, 3, dtype=torch.bool)
+    pose, size = torch.zeros(1, 3, 3), torch.tensor([4.0, 2.0, 1.5]).expand(1, 3, 3)
+    for mode in (True, False):
+        assert torch.equal(CR.term(valid, pose, size, mode), torch.zeros(1, 3, dtype=torch.float64))
+        assert torch.equal(CR.grad(valid, pose, size, mode), torch.zeros(1, 3, 3, dtype=torch.float64))
+
+
+@pytest.mark.parametrize("mode", [True, False])
+def test_constructors_accept_the_collision_term(tb, mode):
+    """DifferentiableReward and WaymoMotion with w_collision > 0 (both raised NotImplementedError before the term existed)."""
+    R = import_module("trafficbots_amd.utils.rewards")
+    il = dict(l_pos=dict(weight=1e-1, criterion="SmoothL1Loss"), l_rot=dict(weight=1e1, criterion="SmoothL1Loss", angular_type="cosine"),
+              l_spd=dict(weight=1e-1, criterion="SmoothL1Loss"))
+    dr = R.DifferentiableReward(w_collision=0.5, use_il_loss=True, reduce_collsion_with_max=mode, **il)
+    assert dr.w_collision == 0.5 and dr.reduce_collsion_with_max == mode
+    with pytest.raises(ValueError):
+        dr.get(torch.ones(1, 2, dtype=torch.bool), torch.zeros(1, 2, 3), torch.zeros(1, 2, 3), None, None, None, ag_size=None)
+    W = import_module("trafficbots_amd.pl_modules.waymo_motion")
+    scfg = tb.config.default_sim_cfg()
+    scfg["differentiable_reward"]["w_collision"] = 0.5
+    scfg["differentiable_reward"]["reduce_collsion_with_max"] = mode
+    wm = W.WaymoMotion(model=tb.config.default_model_cfg(n_tgt_knn=4), data_size=tb.synthetic.DATA_SIZE, **scfg)
+    assert wm.diffbar_reward.w_collision == 0.5
+    scfg["differentiable_reward"]["use_il_loss"] = False  # the other clauses of the refusal stay
+    with pytest.raises(NotImplementedError):
+        W.WaymoMotion(model=tb.config.default_model_cfg(n_tgt_knn=4), data_size=tb.synthetic.DATA_SIZE, **scfg)
+
+
+def test_entry_points_are_declared_bound_and_refuse_bad_arguments(tb):
+    """The three entry points of include/tbx_hip_reward.h: declared in a header tbx_hip.h includes, exported by libtbx_hip_reward.so - and by
+    it alone: libtbx_hip.so's export list stays ABI 7 + tbx_rollout_metrics -, bound with argtypes; NULL pointers / impossible sizes / too
+    many agents come back as codes before anything is launched (no GPU here; the stand-in pointers are never read)."""
+    import subprocess
+
+    hip = import_module("trafficbots_amd.hip")
+    main, lib = hip.load(), hip.load_reward()
+    names = ["tbx_collision_reward_bwd", "tbx_collision_reward_fwd", "tbx_train_chain_bwd_pose"]
+    assert hip.reward_symbols() == names and not set(names) & set(hip.declared_symbols() + hip.extension_symbols())
+    assert '#include "tbx_hip_reward.h"' in hip.HEADER_PATH.read_text() and main.tbx_version() == 7
+
+    def exported(path):
+        nm = subprocess.run(["nm", "-D", "--defined-only", str(path)], check=True, capture_output=True, text=True).stdout
+        return sorted(l.split()[2] for l in nm.splitlines() if len(l.split()) == 3 and l.split()[1] == "T")
+
+    assert exported(hip.REWARD_LIB_PATH) == names and not set(names) & set(exported(hip.LIB_PATH))
+    assert (len(lib.tbx_collision_reward_fwd.argtypes), len(lib.tbx_collision_reward_bwd.argtypes), len(lib.tbx_train_chain_bwd_pose.argtypes)) == (20, 21, 8)
+    ext = hip.REWARD_HEADER_PATH.read_text()
+    assert f"#define TBX_COLLISION_MAX_AG {hip.COLLISION_MAX_AG}" in ext and f"#define TBX_COLLISION_LANES {hip.COLLISION_LANES}" in ext
+    assert hip.COLLISION_MAX_AG >= 256
+    P, cap = 0x10000, hip.COLLISION_MAX_AG
+    fwd = lambda pose=P, rows=2, n_k=1, A=5, ps=(45, 3, 15), c=P: lib.tbx_collision_reward_fwd(pose, P, rows, n_k, A, 3, *ps, 15, 1, 5, P, 1, c, 15, 1, 5, None, None)
+    assert fwd(pose=None) == -1 and fwd(c=None) == -1 and fwd(rows=3, n_k=2) == -1 and fwd(A=0) == -1 and fwd(ps=(45, 2, 15)) == -1
+    assert fwd(A=cap + 1) == -2
+    bwd = lambda arg=P, d=P, A=5: lib.tbx_collision_reward_bwd(P, P, 2, 1, A, 3, 45, 3, 15, 15, 1, 5, P, 1, P, 15, 1, 5, arg, d, None)
+    assert bwd(arg=None) == -1 and bwd(d=None) == -1 and bwd(A=cap + 1) == -2
+    assert lib.tbx_train_chain_bwd_pose(None, P, 1, 1, P, None, P, None) == -1

@@ -1,0 +1,234 @@
+"""GPU checks of the collision term of the differentiable reward at the kernel level: tbx_collision_reward_fwd / _bwd
+(csrc/collision.hip) against the reference's recorded outputs (tests/golden/collision_reward.npz) and the float64 restatement
+(tests/collision_ref.py), their edge semantics and argument checks, and `DifferentiableReward.get` with the term on.
+
+Tolerances: 8 x the reference's own float32 - float64 difference + 1e-7 on the term, + 1e-6 on the gradient; the gradient
+on the agents whose discrete decisions are not within rounding of flipping (collision_ref.inside_margins), finite everywhere."""
+import functools
+import sys
+from importlib import import_module
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import collision_ref as CR  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+CASES = ["s3_a5_w8", "s2_a64_w60", "s2_a65_w40", "s4_a33_w25", "s2_a128_w120", "s1_a1_w1"]
+T = 3  # the golden case is step 1 of a three-step log; steps 0 / 2 are perturbed copies, compared with the restatement
+
+
+@pytest.fixture(scope="module")
+def hip(tb):
+    h = import_module("trafficbots_amd.hip")
+    h.load()
+    return h
+
+
+@functools.lru_cache(maxsize=None)
+def _golden():
+    return np.load(Path(__file__).resolve().parent / "golden" / "collision_reward.npz")
+
+
+@functools.lru_cache(maxsize=None)
+def _log(name):
+    """The three-step log of a golden case (CPU, float32): valid [n, T, A], pose [n, T, A, 3], ag_size [n, A, 3], weight [n, T, A]."""
+    g = _golden()
+    valid, pose, size = (torch.from_numpy(g[f"{name}/{k}"]) for k in ("pred_valid", "pred_pose", "ag_size"))
+    n, A = valid.shape
+    gen = torch.Generator().manual_seed(len(name))
+    before = pose * torch.tensor([0.9, 0.9, 1.0]) + torch.randn(n, A, 3, generator=gen) * 0.05  # denser
+    after = pose * torch.tensor([1.2, 1.2, -1.0])                                                 # sparser, mirrored headings
+    v0 = valid & (torch.rand(n, A, generator=gen) < 0.9)
+    w = CR.upstream_weight(n, A)
+    return (torch.stack([v0, valid, valid], 1), torch.stack([before, pose, after], 1).contiguous(), size,
+            torch.stack([w.flip(1), w, 2.0 - w], 1).float().contiguous())
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name, mode):
+    """float64 restatement of the whole log (computed once per case and reduction): term [n, T, A], gradient [n, T, A, 3], the agents whose
+    gradient is compared [n, T, A]."""
+    valid, pose, size, w = _log(name)
+    n, _, A = valid.shape
+    term = CR.term_log(valid, pose, size, mode)
+    grad, keep = [], []
+    for t in range(valid.shape[1]):
+        grad.append(CR.grad(valid[:, t], pose[:, t], size, mode, weight=w[:, t].double()))
+        keep.append(CR.inside_margins(CR.margins(valid[:, t], pose[:, t], size, mode)))
+    return term, torch.stack(grad, 1), torch.stack(keep, 1)
+
+
+def _layouts(valid, pose, layout, dev):
+    """The log on the device as [n, T, A(, 3)] VIEWS: 'chain' = dense in that order; 'engine' = steps [2, 2 + T) of an agent-major
+    [n, A, T + 5, 3] log (ld_t > T) filled with NaN / 1 outside the slice - the kernel must not read there."""
+    n, T_, A = valid.shape
+    if layout == "chain":
+        return valid.to(torch.uint8).to(dev).contiguous(), pose.to(dev).contiguous()
+    big_p = torch.full((n, A, T_ + 5, 3), float("nan"), device=dev)
+    big_v = torch.ones(n, A, T_ + 5, dtype=torch.uint8, device=dev)
+    big_p[:, :, 2:2 + T_] = pose.permute(0, 2, 1, 3).to(dev)
+    big_v[:, :, 2:2 + T_] = valid.permute(0, 2, 1).to(torch.uint8).to(dev)
+    return big_v[:, :, 2:2 + T_].permute(0, 2, 1), big_p[:, :, 2:2 + T_].permute(0, 2, 1, 3)
+
+
+@pytest.mark.parametrize("layout", ["chain", "engine"])
+@pytest.mark.parametrize("mode", [True, False], ids=["max", "sum"])
+@pytest.mark.parametrize("name", CASES)
+def test_kernels_vs_golden_and_restatement(hip, name, mode, layout):
+    dev = torch.device("cuda:0")
+    g = _golden()
+    tol_c, tol_g = 8 * float(g["bound_c"]) + 1e-7, 8 * float(g["bound_g"]) + 1e-6
+    valid, pose, size, w = _log(name)
+    ref_c, ref_g, keep = _reference(name, mode)
+    v, p = _layouts(valid, pose, layout, dev)
+    size_d, w_d = size.to(dev), w.to(dev)
+    if layout == "engine":  # the term is written into a slice of an agent-major log as well
+        out_big = torch.full((valid.shape[0], valid.shape[2], T + 2), -7.0, device=dev)
+        c, arg = hip.collision_reward_fwd(p, v, size_d, mode, out=out_big[:, :, 1:1 + T].permute(0, 2, 1))
+        assert bool((out_big[:, :, 0] == -7.0).all()) and bool((out_big[:, :, -1] == -7.0).all())
+    else:
+        c, arg = hip.collision_reward_fwd(p, v, size_d, mode)
+    d = hip.collision_reward_bwd(p, v, size_d, mode, w_d, arg)
+    c2, arg2 = hip.collision_reward_fwd(p, v, size_d, mode)
+    d2 = hip.collision_reward_bwd(p, v, size_d, mode, w_d, arg2)
+    assert torch.equal(c2, c) and torch.equal(d2.view(torch.int32), d.view(torch.int32))  # two calls: bit-equal
+    c, d = c.cpu().double(), d.cpu().double()
+    gold_c, gold_g = torch.from_numpy(g[f"{name}/{'max' if mode else 'sum'}/term"]), torch.from_numpy(g[f"{name}/{'max' if mode else 'sum'}/grad"])
+    gold_keep = CR.inside_margins({k: torch.from_numpy(g[f"{name}/{'max' if mode else 'sum'}/margin_{k}"]) for k in CR.MARGIN_FLOOR})
+    e_gold_c = float((c[:, 1] - gold_c).abs().max())
+    e_gold_g = float(((d[:, 1] - gold_g).abs() * gold_keep[..., None]).max())
+    e_ref_c = float((c - ref_c).abs().max())
+    e_ref_g = float(((d - ref_g).abs() * keep[..., None]).max())
+    print(f"[collision kernels, {name}, {'max' if mode else 'sum'}, {layout}] term: vs golden {e_gold_c:.3g}, vs restatement {e_ref_c:.3g} (bound {tol_c:.3g}); "
+          f"gradient: vs golden {e_gold_g:.3g}, vs restatement {e_ref_g:.3g} (bound {tol_g:.3g}); {int((~keep).sum())} agent-steps outside the margins")
+    assert e_gold_c <= tol_c and e_ref_c <= tol_c
+    assert bool(torch.isfinite(d).all())
+    assert e_gold_g <= tol_g and e_ref_g <= tol_g
+    assert float(c.min()) >= 0.0 and float(c.max()) <= 1.0
+    assert bool((d[~valid] == 0).all()) and bool((c[~valid] == 0).all())  # invalid agents: no term, no gradient
+
+
+@pytest.mark.parametrize("mode", [True, False], ids=["max", "sum"])
+@pytest.mark.parametrize("A", [2, 63, 257])
+def test_kernels_at_further_agent_counts(tb, hip, A, mode):
+    """Against the restatement only: two agents, one short of the 64 agents a pass of the workgroup takes, and more than 256 (five
+    passes, the last one of a single agent)."""
+    dev = torch.device("cuda:0")
+    assert hip.COLLISION_MAX_AG >= 257
+    g = _golden()
+    tol_c, tol_g = 8 * float(g["bound_c"]) + 1e-7, 8 * float(g["bound_g"]) + 1e-6
+    case = tb.synthetic.make_collision_case(2, A, seed=3, spread=3.0 if A == 2 else 5.0 * A ** 0.5)  # (A = 2: one of the two scenes overlaps)
+    valid, pose, size = case["pred_valid"], case["pred_pose"], case["ag_size"]
+    w = CR.upstream_weight(2, A)
+    ref_c, ref_g = CR.term(valid, pose, size, mode), CR.grad(valid, pose, size, mode)
+    keep = CR.inside_margins(CR.margins(valid, pose, size, mode))
+    v, p = valid.to(torch.uint8).to(dev).unsqueeze(1), pose.to(dev).unsqueeze(1)
+    c, arg = hip.collision_reward_fwd(p, v, size.to(dev), mode)
+    d = hip.collision_reward_bwd(p, v, size.to(dev), mode, w.float().to(dev).unsqueeze(1), arg)
+    c, d = c[:, 0].cpu().double(), d[:, 0].cpu().double()
+    e_c, e_g = float((c - ref_c).abs().max()), float(((d - ref_g).abs() * keep[..., None]).max())
+    print(f"[collision kernels, A = {A}, {'max' if mode else 'sum'}] term {e_c:.3g} (bound {tol_c:.3g}), gradient {e_g:.3g} (bound {tol_g:.3g}), "
+          f"{100 * float((ref_c > 0).double().mean()):.0f} % rows non-zero, {int((~keep).sum())} agents outside the margins")
+    assert float((ref_c > 0).double().mean()) > 0.05
+    assert e_c <= tol_c and e_g <= tol_g and bool(torch.isfinite(d).all())
+
+
+def _one_step(hip, valid, pose, size, mode, weight=None):
+    """(c [A], d_pose [A, 3]) of one scene at one step, on the device and back."""
+    dev = torch.device("cuda:0")
+    v = torch.tensor(valid, dtype=torch.uint8, device=dev).view(1, 1, -1)
+    p = torch.tensor(pose, dtype=torch.float32, device=dev).view(1, 1, -1, 3)
+    s = torch.tensor(size, dtype=torch.float32, device=dev).view(1, -1, 3)
+    w = torch.ones(1, 1, v.shape[2], device=dev) if weight is None else torch.tensor(weight, dtype=torch.float32, device=dev).view(1, 1, -1)
+    c, arg = hip.collision_reward_fwd(p, v, s, mode)
+    d = hip.collision_reward_bwd(p, v, s, mode, w, arg)
+    return c[0, 0].cpu(), d[0, 0].cpu()
+
+
+@pytest.mark.parametrize("mode", [True, False], ids=["max", "sum"])
+def test_edge_semantics(hip, mode):
+    eps = float(torch.finfo(torch.float32).eps)
+    car = [4.5, 2.0, 1.6]
+    # two coincident valid agents: the 25 distances' minimum is 0 (+ eps): term 1 (to rounding), gradient exactly 0
+    c, d = _one_step(hip, [1, 1], [[3.0, -2.0, 0.4], [3.0, -2.0, 0.4]], [car, car], mode)
+    expect = 1.0 if mode else 0.5  # sum mode: one partner over two valid agents
+    assert torch.allclose(c, torch.full((2,), expect), atol=1e-6) and torch.equal(d, torch.zeros(2, 3))
+    # square agents (l == w): the five circles coincide, the first minimum is circle pair (0, 0) whose lever arm (k - 2) d is 0 anyway - the
+    # gradient is the one of two discs: along the centre line, none on the yaw; equal and opposite on the two agents
+    sq = [2.0, 2.0, 1.5]
+    c, d = _one_step(hip, [1, 1], [[0.0, 0.0, 0.3], [1.2, 0.0, -1.0]], [sq, sq], mode)
+    r_sum = 2 * (1.0 + eps)
+    c_pair = 1 - (1.2 + eps) / r_sum
+    n_rows = 2.0  # each agent's pose is read by its own row and by the partner's
+    scale = (1.0 if mode else 0.5) * n_rows / r_sum
+    assert torch.allclose(c, torch.full((2,), c_pair if mode else c_pair / 2), atol=1e-6)
+    assert torch.allclose(d, torch.tensor([[scale, 0.0, 0.0], [-scale, 0.0, 0.0]]), atol=1e-6) and bool((d[:, 1:] == 0).all())
+    ref = CR.grad(torch.ones(1, 2, dtype=torch.bool), torch.tensor([[[0.0, 0.0, 0.3], [1.2, 0.0, -1.0]]]), torch.tensor([[sq, sq]]), mode,
+                  weight=torch.ones(1, 2))
+    assert torch.allclose(d.double(), ref[0], atol=1e-6)
+    # a step without a valid agent: 0 and a finite zero gradient (the reference's sum mode gives NaN there)
+    c, d = _one_step(hip, [0, 0, 0], [[0.0, 0.0, 0.0], [0.5, 0.0, 0.0], [0.0, 0.5, 1.0]], [car] * 3, mode)
+    assert torch.equal(c, torch.zeros(3)) and torch.equal(d, torch.zeros(3, 3))
+    # one agent: nothing to collide with
+    c, d = _one_step(hip, [1], [[1.0, 2.0, 3.0]], [car], mode)
+    assert torch.equal(c, torch.zeros(1)) and torch.equal(d, torch.zeros(1, 3))
+    # an invalid agent on top of a valid pair neither receives nor causes anything: same numbers as without it
+    pair = [[0.0, 0.0, 0.2], [2.5, 0.6, 1.1]]
+    c2, d2 = _one_step(hip, [1, 1], pair, [car, car], mode, weight=[0.7, 1.3])
+    c3, d3 = _one_step(hip, [1, 0, 1], [pair[0], [1.0, 0.3, 0.5], pair[1]], [car] * 3, mode, weight=[0.7, 5.0, 1.3])
+    assert float(c2.min()) > 0
+    assert torch.equal(c3[[0, 2]], c2) and float(c3[1]) == 0.0
+    assert torch.equal(d3[[0, 2]], d2) and torch.equal(d3[1], torch.zeros(3))
+
+
+def test_argument_checks_return_codes_without_a_launch(hip):
+    """NULL pointers, sizes and strides that cannot be right, and more agents than the cap: TBX_ERR_ARG / TBX_ERR_UNSUPPORTED before any
+    launch (the stand-in pointers below are never read)."""
+    lib = hip.load_reward()
+    P = 0x10000
+    cap = hip.COLLISION_MAX_AG
+
+    def fwd(pose=P, valid=P, rows=2, n_k=1, A=5, T=3, ps=(45, 3, 15), vs=(15, 1, 5), size=P, c=P, cs=(15, 1, 5)):
+        return lib.tbx_collision_reward_fwd(pose, valid, rows, n_k, A, T, *ps, *vs, size, 1, c, *cs, None, None)
+
+    def bwd(g=P, arg=P, d_pose=P, mode=1, A=5, **kw):
+        return lib.tbx_collision_reward_bwd(P, P, 2, 1, A, 3, 45, 3, 15, 15, 1, 5, P, mode, g, 15, 1, 5, arg, d_pose, None)
+
+    torch.cuda.synchronize()
+    for bad in (dict(pose=None), dict(valid=None), dict(size=None), dict(c=None), dict(rows=0), dict(A=0), dict(T=0), dict(n_k=0),
+                dict(rows=3, n_k=2), dict(ps=(45, 2, 15)), dict(ps=(45, 3, 0)), dict(ps=(0, 3, 15)), dict(vs=(15, 0, 5)), dict(cs=(15, 1, 0)),
+                dict(cs=(-15, 1, 5))):
+        assert fwd(**bad) == -1, bad
+    assert fwd(A=cap + 1, ps=(3 * 3 * (cap + 1), 3, 3 * (cap + 1)), vs=(3 * (cap + 1), 1, cap + 1), cs=(3 * (cap + 1), 1, cap + 1)) == -2
+    assert bwd(g=None) == -1 and bwd(d_pose=None) == -1 and bwd(arg=None, mode=1) == -1 and bwd(A=cap + 1) == -2
+    assert lib.tbx_train_chain_bwd_pose(None, P, 1, 1, P, None, P, None) == -1
+    assert torch.cuda.current_stream().query()  # nothing was enqueued
+
+
+@pytest.mark.parametrize("il", [True, False], ids=["il", "no_il"])
+@pytest.mark.parametrize("mode", [True, False], ids=["max", "sum"])
+def test_differentiable_reward_get_equals_the_reference(tb, hip, mode, il):
+    """`DifferentiableReward.get` stand-alone, one step, w_collision = 0.7, against the reference's recorded dicts."""
+    dev = torch.device("cuda:0")
+    R = import_module("trafficbots_amd.utils.rewards")
+    g = _golden()
+    tol_c = 8 * float(g["bound_c"]) + 1e-7
+    dr = R.DifferentiableReward(l_pos=dict(weight=1e-1, criterion="SmoothL1Loss"), l_rot=dict(weight=1e1, criterion="SmoothL1Loss", angular_type="cosine"),
+                                l_spd=dict(weight=1e-1, criterion="SmoothL1Loss"), w_collision=float(g["w_collision"]), use_il_loss=il,
+                                reduce_collsion_with_max=mode)
+    for name in CASES:
+        c = {k: torch.from_numpy(g[f"{name}/{k}"]).to(dev) for k in ("pred_valid", "pred_pose", "pred_motion", "gt_valid", "gt_pose", "gt_motion", "ag_size")}
+        got = dr.get(**c)
+        assert set(got) == {"diffbar_reward_valid", "diffbar_reward", "r_imitation_pos", "r_imitation_rot", "r_imitation_spd", "r_traffic_rule_approx"}
+        for k, v in got.items():
+            ref = torch.from_numpy(g[f"{name}/{'max' if mode else 'sum'}/get_il{int(il)}/{k}"])
+            if k == "diffbar_reward_valid":
+                assert torch.equal(v.cpu(), ref) and torch.equal(ref, c["pred_valid"].cpu()), (name, k)
+            elif k == "r_traffic_rule_approx":
+                assert float((v.cpu().double() - ref).abs().max()) <= tol_c, (name, k)
+            else:  # the imitation terms: float32 expressions of values up to ~10 (rtol as tests/test_hip_parity.py holds tbx_diffbar_reward to)
+                torch.testing.assert_close(v.cpu().double(), ref, rtol=1e-5, atol=1e-5 + (tol_c if k == "diffbar_reward" else 0.0))

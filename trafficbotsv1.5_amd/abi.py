@@ -11,7 +11,9 @@ from typing import List
 _lib = None
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "csrc" / "libtbx_hip.so"
+REWARD_LIB_PATH = _PKG / "csrc" / "libtbx_hip_reward.so"  # the entry points of include/tbx_hip_reward.h: a library of their own
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
+REWARD_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_reward.h"
 EXTENSION_HEADER_PATHS = (HEADER_PATH.parent / "tbx_hip_metrics.h",)  # included by tbx_hip.h: entry points added after ABI 7 was laid down
 
 # ---- constants mirrored from include/tbx_hip.h
@@ -203,6 +205,7 @@ class RuleCtx(C.Structure):
 
 
 RULE_COLLIDED, RULE_COLLIDED_WOSAC, RULE_RUN_ROAD_EDGE, RULE_RUN_RED_LIGHT, RULE_PASSIVE = 1, 2, 4, 8, 16
+COLLISION_MAX_AG, COLLISION_LANES = 512, 4  # TBX_COLLISION_* of include/tbx_hip_reward.h: the collision kernels' agent cap / lanes per agent
 METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
 
 _lib = None
@@ -225,6 +228,40 @@ def extension_symbols() -> List[str]:
     if missing:
         raise ImportError(f"include/tbx_hip.h does not include {missing}")
     return sorted({s for p in EXTENSION_HEADER_PATHS for s in re.findall(_DECL, p.read_text(), flags=re.M)})
+
+
+def reward_symbols() -> List[str]:
+    """Entry points declared in include/tbx_hip_reward.h: what libtbx_hip_reward.so exports."""
+    return sorted(set(re.findall(_DECL, REWARD_HEADER_PATH.read_text(), flags=re.M)))
+
+
+_reward_lib = None
+
+
+def load_reward():
+    """dlopen the in-tree libtbx_hip_reward.so (the collision term's kernel pair, the training chain's reverse walk with a pose adjoint) and
+    check it exports every symbol its header declares. No GPU needed. A missing library is an error: there is no fallback path."""
+    global _reward_lib
+    if _reward_lib is not None:
+        return _reward_lib
+    load()  # (the error strings / ABI version check of the main library)
+    if not REWARD_LIB_PATH.exists():
+        raise ImportError(f"{REWARD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`. There is no fallback path.")
+    lib = C.CDLL(str(REWARD_LIB_PATH))
+    for s in reward_symbols():
+        if not hasattr(lib, s):
+            raise ImportError(f"libtbx_hip_reward.so does not export {s}")
+    i32, i64, vp = C.c_int, C.c_int64, C.c_void_p
+    lib.tbx_collision_reward_fwd.argtypes = [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, vp, i32, vp, i64, i64, i64, vp, vp]
+    lib.tbx_collision_reward_bwd.argtypes = [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, vp, i32, vp, i64, i64, i64, vp, vp, vp]
+    lib.tbx_train_chain_bwd_pose.argtypes = [C.POINTER(TrainChainArgs), vp, i64, i64, vp, vp, vp, vp]
+    untyped = [s for s in reward_symbols() if getattr(lib, s).argtypes is None]
+    if untyped:
+        raise ImportError(f"abi.load_reward(): no argtypes for {untyped}")
+    for s in reward_symbols():
+        getattr(lib, s).restype = C.c_int
+    _reward_lib = lib
+    return lib
 
 
 def load():

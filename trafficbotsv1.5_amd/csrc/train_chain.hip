@@ -21,6 +21,7 @@ __device__ __forceinline__ float sl1(float d) {  // F.smooth_l1_loss, beta = 1
 }
 __device__ __forceinline__ float sl1_grad(float d) { return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f); }
 
+#ifndef TBX_REWARD_EXT  // (the reward extension's build of this file holds the reverse walk only, see the end of the file)
 // The policy inputs of the NEXT step in the layout the policy reads them in (tbx_train_chain_fwd_windows): the W-step windows [n, A, W
 // (, 3)], oldest first, and the current validity / navigation flags - written by the thread that owns the agent, behind its step (the
 // stepping pass spent six strided-copy launches per closed-loop step on these).
@@ -161,11 +162,13 @@ __global__ __launch_bounds__(64) void train_chain_fwd_kernel(const tbx_train_cha
   }
 }
 
+#endif  // !TBX_REWARD_EXT
+
 // d(mean) from d(reward), all steps, in reverse. Reads what the forward over [0, T) left behind: the records of the state
 // before every step (slot window - 1 + t holds the state before step t + 1), the override flags and the predictions.
 __global__ __launch_bounds__(64) void train_chain_bwd_kernel(const tbx_train_chain_t c, const float* __restrict__ mean, int64_t sn,
                                                              int64_t st, const float* __restrict__ d_reward,
-                                                             float* __restrict__ d_mean) {
+                                                             const float* __restrict__ d_pred_pose, float* __restrict__ d_mean) {
 #pragma clang fp contract(off)
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
@@ -195,6 +198,8 @@ __global__ __launch_bounds__(64) void train_chain_bwd_kernel(const tbx_train_cha
         dw += g * 0.5f * c.w_rot * sinf(c.gt_pose[ig * 3 + 2] - nw);
         dv += g * c.w_spd * sl1_grad(c.gt_motion[ig * 3] - nv);
       }
+      // an adjoint of the prediction from outside the chain (tbx_train_chain_bwd_pose: the collision term reads pred_pose)
+      if (d_pred_pose != nullptr) dx += d_pred_pose[it * 3], dy += d_pred_pose[it * 3 + 1], dw += d_pred_pose[it * 3 + 2];
       const float pw = c.rec_pose[ir * 3 + 2], mv = c.rec_motion[ir * 3];
       const float u0 = tanhf(mean[b * sn + t * st + a * 2]), u1 = tanhf(mean[b * sn + t * st + a * 2 + 1]);
       const float acc = u0 * lim0, yr = u1 * lim1;
@@ -227,6 +232,18 @@ int check(const tbx_train_chain_t* c) {
 
 }  // namespace
 
+// The reverse walk's launch: tbx_train_chain_bwd (d_pred_pose = nullptr) and tbx_train_chain_bwd_pose are the same kernel.
+static int launch_bwd(const tbx_train_chain_t* c, const float* mean, int64_t mean_stride_n, int64_t mean_stride_t, const float* d_reward,
+                      const float* d_pred_pose, float* d_mean, void* stream) {
+  const int rc = check(c);
+  if (rc != TBX_OK) return rc;
+  if (!mean || !d_reward || !d_mean) return TBX_ERR_ARG;
+  hipLaunchKernelGGL(train_chain_bwd_kernel, dim3((c->n_ag + 63) / 64, c->n_batch), dim3(64), 0, (hipStream_t)stream, *c, mean,
+                     mean_stride_n, mean_stride_t, d_reward, d_pred_pose, d_mean);
+  return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
+}
+
+#ifndef TBX_REWARD_EXT
 extern "C" int tbx_train_chain_fwd(const tbx_train_chain_t* c, const float* mean, int64_t mean_stride_n, int64_t mean_stride_t, int t0,
                                    int t1, void* stream) {
   const int rc = check(c);
@@ -251,10 +268,13 @@ extern "C" int tbx_train_chain_fwd_windows(const tbx_train_chain_t* c, const flo
 
 extern "C" int tbx_train_chain_bwd(const tbx_train_chain_t* c, const float* mean, int64_t mean_stride_n, int64_t mean_stride_t,
                                    const float* d_reward, float* d_mean, void* stream) {
-  const int rc = check(c);
-  if (rc != TBX_OK) return rc;
-  if (!mean || !d_reward || !d_mean) return TBX_ERR_ARG;
-  hipLaunchKernelGGL(train_chain_bwd_kernel, dim3((c->n_ag + 63) / 64, c->n_batch), dim3(64), 0, (hipStream_t)stream, *c, mean,
-                     mean_stride_n, mean_stride_t, d_reward, d_mean);
-  return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
+  return launch_bwd(c, mean, mean_stride_n, mean_stride_t, d_reward, nullptr, d_mean, stream);
 }
+#else
+// libtbx_hip_reward.so (include/tbx_hip_reward.h): this file compiled once more with TBX_REWARD_EXT - the same reverse-walk kernel, launched
+// with the adjoint of the predicted pose. libtbx_hip.so's export list stays the one of ABI 7 + tbx_rollout_metrics.
+extern "C" int tbx_train_chain_bwd_pose(const tbx_train_chain_t* c, const float* mean, int64_t mean_stride_n, int64_t mean_stride_t,
+                                        const float* d_reward, const float* d_pred_pose, float* d_mean, void* stream) {
+  return launch_bwd(c, mean, mean_stride_n, mean_stride_t, d_reward, d_pred_pose, d_mean, stream);
+}
+#endif

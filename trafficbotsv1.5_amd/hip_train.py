@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
-from .abi import load  # noqa: F401
+from .abi import load, load_reward  # noqa: F401
 from .hip_base import Seg, _attn_args, _check, _cptr, _derived, _name, _ptr, drop_mix, drop_rate, drop_stream_key, drop_struct, packed_weight, stream_ptr
 
 
@@ -322,3 +322,45 @@ def train_chain_fwd_windows(args: TrainChainArgs, mean: Optional[torch.Tensor], 
 def train_chain_bwd(args: TrainChainArgs, mean: torch.Tensor, stride_n: int, stride_t: int, d_reward: torch.Tensor, d_mean: torch.Tensor):
     _check(load().tbx_train_chain_bwd(C.byref(args), _ptr(mean, torch.float32), stride_n, stride_t, _ptr(d_reward, torch.float32),
                                       _ptr(d_mean, torch.float32), stream_ptr()), "tbx_train_chain_bwd")
+
+
+def train_chain_bwd_pose(args: TrainChainArgs, mean: torch.Tensor, stride_n: int, stride_t: int, d_reward: torch.Tensor,
+                         d_pred_pose: Optional[torch.Tensor], d_mean: torch.Tensor):
+    """tbx_train_chain_bwd_pose: the reverse walk with d_pred_pose [n,T,A,3] (None: tbx_train_chain_bwd) added to the predictions' adjoint."""
+    _check(load_reward().tbx_train_chain_bwd_pose(C.byref(args), _ptr(mean, torch.float32), stride_n, stride_t, _ptr(d_reward, torch.float32),
+                                           _cptr(d_pred_pose, torch.float32), _ptr(d_mean, torch.float32), stream_ptr()), "tbx_train_chain_bwd_pose")
+
+
+def _collision_log_args(pose: torch.Tensor, valid: torch.Tensor, ag_size: torch.Tensor, n_k: int):
+    """The shared leading arguments of tbx_collision_reward_fwd / _bwd for views pose [rows, T, A, 3] f32 / valid [rows, T, A] u8 or bool of
+    any strides (the xyz triple contiguous): a permuted time slice of an agent-major log is read where it lies."""
+    rows, T, A, three = pose.shape
+    assert three == 3 and pose.stride(3) == 1 and tuple(valid.shape) == (rows, T, A) and valid.dtype in (torch.uint8, torch.bool)
+    assert ag_size.dtype == torch.float32 and ag_size.is_contiguous() and tuple(ag_size.shape) == (rows // n_k, A, 3)
+    return (_ptr(pose, torch.float32), _ptr(valid), rows, int(n_k), A, T, pose.stride(0), pose.stride(2), pose.stride(1), valid.stride(0),
+            valid.stride(2), valid.stride(1), _ptr(ag_size))
+
+
+def collision_reward_fwd(pose: torch.Tensor, valid: torch.Tensor, ag_size: torch.Tensor, reduce_with_max: bool, n_k: int = 1,
+                         out: Optional[torch.Tensor] = None, want_arg: bool = True):
+    """tbx_collision_reward_fwd -> (c [rows, T, A] f32 - the unweighted term, written into the view `out` if given -, arg int32 [rows, T, A]
+    | None: the max mode's partner, for collision_reward_bwd)."""
+    rows, T, A, _ = pose.shape
+    c = torch.empty(rows, T, A, dtype=torch.float32, device=pose.device) if out is None else out
+    assert tuple(c.shape) == (rows, T, A) and c.dtype == torch.float32
+    arg = torch.empty(rows, T, A, dtype=torch.int32, device=pose.device) if (want_arg and reduce_with_max) else None
+    _check(load_reward().tbx_collision_reward_fwd(*_collision_log_args(pose, valid, ag_size, n_k), int(bool(reduce_with_max)), _ptr(c), c.stride(0),
+                                           c.stride(2), c.stride(1), _ptr(arg), stream_ptr()), "tbx_collision_reward_fwd")
+    return c, arg
+
+
+def collision_reward_bwd(pose: torch.Tensor, valid: torch.Tensor, ag_size: torch.Tensor, reduce_with_max: bool, g: torch.Tensor,
+                         arg: Optional[torch.Tensor], n_k: int = 1) -> torch.Tensor:
+    """tbx_collision_reward_bwd -> d_pose [rows, T, A, 3] (dense) from g = dL/dc, a [rows, T, A] view of any strides."""
+    rows, T, A, _ = pose.shape
+    assert tuple(g.shape) == (rows, T, A) and g.dtype == torch.float32
+    assert arg is None or (arg.is_contiguous() and tuple(arg.shape) == (rows, T, A))
+    d_pose = torch.empty(rows, T, A, 3, dtype=torch.float32, device=pose.device)
+    _check(load_reward().tbx_collision_reward_bwd(*_collision_log_args(pose, valid, ag_size, n_k), int(bool(reduce_with_max)), _ptr(g), g.stride(0),
+                                           g.stride(2), g.stride(1), _ptr(arg, torch.int32), _ptr(d_pose), stream_ptr()), "tbx_collision_reward_bwd")
+    return d_pose

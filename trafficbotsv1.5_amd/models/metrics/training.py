@@ -62,6 +62,9 @@ class TrainingMetrics(nn.Module):
                 self.dr_il_pos += buffer.diffbar_reward["r_imitation_pos"].sum()
                 self.dr_il_rot += buffer.diffbar_reward["r_imitation_rot"].sum()
                 self.dr_il_spd += buffer.diffbar_reward["r_imitation_spd"].sum()
+                # ASSIGNED, not accumulated, as in the reference (metrics/training.py:143): over an epoch of several updates the reported
+                # value is the LAST update's sum over the whole epoch's counter
+                self.dr_rule_apx = buffer.diffbar_reward["r_traffic_rule_approx"].sum()
         if self.train_navi:
             nv = navi_pred.valid & any_valid
             self.navi_loss = self.navi_loss + (-navi_pred.log_prob(navi_gt)).masked_fill(~nv, 0).sum()

@@ -31,7 +31,7 @@ from ..models.traffic_bots import TrafficBots
 from ..utils.buffer import RolloutBuffer
 from ..utils.dynamics import Dynamics
 from ..utils.rewards import DifferentiableReward
-from ..utils.rollout_engine import RolloutEngine
+from ..utils.rollout_engine import RolloutEngine, add_collision_term
 from ..utils.teacher_forcing import TeacherForcing
 from ..utils.traffic_rule_checker import TrafficRuleChecker
 
@@ -82,12 +82,12 @@ class WaymoMotion(LightningModule):
             raise NotImplementedError("training_deterministic_action=False: sampled actions in the training rollout are not implemented "
                                       "(the default is the deterministic action)")
         self.save_hyperparameters()  # self.hparams.<constructor argument>, as in the reference (waymo_motion.py:66)
-        # tbx_sim_step / tbx_train_chain log the DEFAULT DifferentiableReward (rewards.py:35-85: SmoothL1 position / speed terms, a
-        # cosine SmoothL1 rotation term, no collision approximation); anything else would yield a plausible but wrong RolloutBuffer
+        # tbx_sim_step / tbx_train_chain log the DEFAULT imitation terms of DifferentiableReward (rewards.py:35-74: SmoothL1 position /
+        # speed terms, a cosine SmoothL1 rotation term); anything else would yield a plausible but wrong RolloutBuffer. The collision
+        # approximation (w_collision > 0, rewards.py:76-154) is a launch of its own over the finished pose log (tbx_collision_reward_*).
         rc = to_attr(dict(differentiable_reward))
-        if not rc.get("is_enabled", True) or rc.get("w_collision", 0) > 0 or not rc.get("use_il_loss", True):
-            raise NotImplementedError("differentiable_reward: only the default configuration (is_enabled, use_il_loss, w_collision = 0) "
-                                      "is implemented in the HIP state machine")
+        if not rc.get("is_enabled", True) or not rc.get("use_il_loss", True):
+            raise NotImplementedError("differentiable_reward: only is_enabled with use_il_loss is implemented in the HIP state machine")
         for term, ang in (("l_pos", None), ("l_rot", "cosine"), ("l_spd", None)):
             t = rc[term]
             if t.get("criterion", "SmoothL1Loss") != "SmoothL1Loss" or (ang is not None and t.get("angular_type", ang) != ang):
@@ -208,7 +208,7 @@ class WaymoMotion(LightningModule):
             eng = self.begin_rollout(ag_tokens, mp_tokens, tl_tokens, tl_state_gt, teacher_forcing, rule_checker, step_end,
                                      deterministic_action=deterministic_action)
             eng.run(step_end, use_graph=use_graph)
-            return eng.buffer(self.hp.time_step_current, rule_checker=rule_checker)
+            return eng.buffer(self.hp.time_step_current, rule_checker=rule_checker, collision=self._collision_args(ag_tokens, rule_checker))
         # ---- the reference's loop, statement by statement (waymo_motion.py:218-311)
         teacher_forcing.init(ag_valid=ag_tokens["gt_valid"], ag_pose=ag_tokens["gt_pose"], ag_motion=ag_tokens["gt_motion"],
                              tl_state=tl_state_gt, current_epoch=self.current_epoch)
@@ -240,7 +240,22 @@ class WaymoMotion(LightningModule):
             dyn.disable_ag(violation, _gt_valid)
             dyn.disable_navi(violation)
         buf.finish()
+        col = self._collision_args(ag_tokens, rule_checker)
+        if col is not None:  # the term that couples the agents: one launch over the finished log, as the engine's own loop does
+            add_collision_term(buf.diffbar_reward, buf.pred_valid, buf.pred_pose, col[2], col[0], col[1])
         return buf
+
+    def _collision_args(self, ag_tokens: Dict[str, Tensor], rule_checker=None):
+        """RolloutEngine.buffer's `collision`: (w_collision, reduce_collsion_with_max, ag_size [rows, n_ag, 3]) with the term on, else None."""
+        r = self.diffbar_reward
+        if not (r.is_enabled and r.w_collision > 0):
+            return None
+        size = ag_tokens.get("ag_size")
+        if size is None and rule_checker is not None:
+            size = rule_checker.ag_size
+        if size is None:
+            raise ValueError("differentiable_reward.w_collision > 0 needs ag_tokens['ag_size'] (the batch's ref/ag_size)")
+        return float(r.w_collision), bool(r.reduce_collsion_with_max), size
 
     def forward(self, mp_tokens: Dict[str, Tensor], tl_tokens: Dict[str, Tensor], ag_override: Dict[str, Tensor],
                 tl_override: Dict[str, Tensor], player_override: Optional[Dict[str, Tensor]] = None,

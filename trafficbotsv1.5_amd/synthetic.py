@@ -265,3 +265,32 @@ def make_wosac_keys(n_sc: int = 1, n_ag: int = 64, seed: int = 0, n_ag_no_sim: i
         "history/agent_no_sim/pos": pos0 + vel * t,
         "history/agent_no_sim/yaw_bbox": yaw0 + rate * t,  # (not wrapped: some leave [-pi, pi) so that the transform's wrap is exercised)
     }
+
+
+def make_collision_case(n_sc: int = 2, n_ag: int = 64, seed: int = 0, spread: float = 60.0) -> Dict[str, torch.Tensor]:
+    """Seeded one-step inputs of `DifferentiableReward.get` with the collision term on: poses uniform in a square of side `spread` (the
+    smaller it is for a given agent count, the more five-circle footprints overlap), length 0.5 - 5.5 m, width 0.4 - 2.4 m (independent:
+    a few agents are wider than long, which the min / max of the first two sizes must sort out), about 85 % of the agents valid; a ground
+    truth near the prediction for the imitation terms. float32 / bool, [n_sc, n_ag(, 3)]."""
+    g = torch.Generator().manual_seed(50_000 + seed)
+    U = lambda *s: torch.rand(*s, generator=g)
+    pose = torch.cat([(U(n_sc, n_ag, 2) - 0.5) * spread, (U(n_sc, n_ag, 1) - 0.5) * 2 * math.pi], -1)
+    size = torch.cat([0.5 + 5.0 * U(n_sc, n_ag, 1), 0.4 + 2.0 * U(n_sc, n_ag, 1), 1.0 + U(n_sc, n_ag, 1)], -1)
+    motion = torch.cat([U(n_sc, n_ag, 1) * 15.0, (U(n_sc, n_ag, 2) - 0.5) * 2.0], -1)
+    gt_pose = pose + torch.randn(n_sc, n_ag, 3, generator=g) * torch.tensor([1.5, 1.5, 0.3])
+    gt_motion = motion + torch.randn(n_sc, n_ag, 3, generator=g) * 1.5
+    return {"pred_valid": U(n_sc, n_ag) < 0.85, "pred_pose": pose, "pred_motion": motion, "gt_valid": U(n_sc, n_ag) < 0.8, "gt_pose": gt_pose,
+            "gt_motion": gt_motion, "ag_size": size}
+
+
+def crowd_scene(batch: Dict[str, torch.Tensor], pull: float = 0.06, size_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+    """A copy of a `make_scene` batch whose agents START close together: every trajectory is shifted rigidly so that its first position
+    moves from xy0 to pull * xy0 (speeds, headings, the map and the destinations stay), and the sizes are scaled by `size_scale`. At
+    pull = 0.06 the 150 m square of starts becomes 9 m: the five-circle footprints overlap over the first seconds of a rollout, which
+    the collision term of the differentiable reward needs to be exercised. Deterministic; `make_scene` itself is untouched."""
+    out = {k: v.clone() for k, v in batch.items()}
+    shift = batch["agent/pos"][:, :, :1, :2] * (1.0 - pull)  # [n_sc, n_ag, 1, 2]
+    out["agent/pos"][..., :2] -= shift
+    out["agent/goal"][..., :2] -= shift[:, :, 0]
+    out["agent/size"] *= size_scale
+    return out

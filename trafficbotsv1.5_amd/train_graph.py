@@ -488,7 +488,18 @@ def training_rollout(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, step_end
         disabled = disabled | dis
         valid = valid & ~dis
         navi_valid = navi_valid & ~reach_now
-    return {k: torch.stack(v, 2) for k, v in out.items()}
+    ro = {k: torch.stack(v, 2) for k, v in out.items()}
+    col = collision_config(wm, b) if record is None else None  # (a stepping pass only records the policy inputs: nothing new there)
+    if col is not None and ro["pred_pose"].is_cuda:
+        # rewards.py:76-83 for all steps at once from the finished log (the term never feeds back into the state): the kernel pair of the
+        # fused chain through CollisionRewardFn, on the agent-major log where it lies
+        w, reduce_max, ag_size = col
+        c = CollisionRewardFn.apply(ro["pred_pose"].permute(0, 2, 1, 3), ro["pred_valid"].permute(0, 2, 1), ag_size, reduce_max)
+        ro["rule_apx"] = (c.permute(0, 2, 1) * (-w)).masked_fill(~ro["pred_valid"], 0.0)
+        ro["reward"], ro["reward_valid"] = ro["reward"] + ro["rule_apx"], ro["pred_valid"]
+    elif col is not None:
+        raise RuntimeError("differentiable_reward.w_collision > 0: the collision term is a HIP kernel pair; there is no CPU path")
+    return ro
 
 
 def tl_nll_all_steps(logits: Tensor, tl_gt: Tensor, tl_invalid: Tensor):
@@ -682,7 +693,10 @@ def training_loss(cfg, ro, navi_pred: DestCategorical, navi_gt, post: DiagGaussi
     tl = cfg.w_tl_state * ro["tl_nll"].masked_fill(~tv, 0).sum() / cnt(tv)
     if counts is not None:
         counts.update(vae_kl=kv.sum(), diffbar_reward=rv.sum(), navi_loss=nv.sum(), tl_state_loss=tv.sum())
-    return {"loss": vae_kl - reward + navi + tl, "vae_kl": vae_kl, "diffbar_reward": reward, "navi_loss": navi, "tl_state_loss": tl}
+    out = {"loss": vae_kl - reward + navi + tl, "vae_kl": vae_kl, "diffbar_reward": reward, "navi_loss": navi, "tl_state_loss": tl}
+    if "rule_apx" in ro:  # metrics/training.py:143,177 (w_collision > 0): the whole log's sum over the reward's counter, for the logs only
+        out["dr_rule_apx"] = ro["rule_apx"].detach().sum() / cnt(rv)
+    return out
 
 
 def training_step(wm, raw_batch: Dict[str, Tensor], noise: Optional[Tensor] = None, use_prior: Optional[Tensor] = None) -> Dict[str, Tensor]:

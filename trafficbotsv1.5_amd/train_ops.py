@@ -650,6 +650,10 @@ class TrainChain:
         self.win = dict(hv=z(n, A, W, dt=u8), hp=z(n, A, W, 3), hm=z(n, A, W, 3), valid=torch.zeros(n, A, dtype=torch.bool, device=dev),
                         navi_valid=torch.zeros(n, A, dtype=torch.bool, device=dev))
         self._win_step = 0  # the step whose inputs self.win holds (0: none)
+        # the reward term that couples the agents (w_collision > 0): (weight, reduce_with_max, ag_size [n, A, 3]) - computed by TrainChainFn
+        # from the finished pred_pose log in a launch of its own, not by the chain (the term never feeds back into the state)
+        self.collision = collision_config(wm, b)
+        self.rule_apx: Optional[Tensor] = None  # the weighted term [n, T, A] of the last differentiated pass
         self.reset()
 
     def reset(self) -> None:
@@ -702,8 +706,11 @@ class TrainChain:
         """The rollout log in training_rollout's layout ([n, A, T(,3)])."""
         t = self.t
         p = lambda x: x.permute(0, 2, 1) if x.dim() == 3 else x.permute(0, 2, 1, 3)
-        return {"pred_valid": p(t["pred_valid"]).bool(), "pred_pose": p(t["pred_pose"]), "pred_motion": p(t["pred_motion"]),
-                "reward": p(reward), "reward_valid": p(t["reward_valid"]).bool(), "tf": p(t["tf"]).bool()}
+        out = {"pred_valid": p(t["pred_valid"]).bool(), "pred_pose": p(t["pred_pose"]), "pred_motion": p(t["pred_motion"]),
+               "reward": p(reward), "reward_valid": p(t["reward_valid"]).bool(), "tf": p(t["tf"]).bool()}
+        if self.collision is not None:  # rewards.py:76-83: the loss averages over the prediction's validity; the term for the logs
+            out["reward_valid"], out["rule_apx"] = out["pred_valid"], p(self.rule_apx)
+        return out
 
 
 class TrainChainFn(torch.autograd.Function):
@@ -716,13 +723,59 @@ class TrainChainFn(torch.autograd.Function):
         chain.reset()
         hip.train_chain_fwd(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, 0, chain.T)
         ctx.chain = chain
-        ctx.save_for_backward(mean)
-        return chain.t["reward"].clone()
+        if chain.collision is None:
+            ctx.save_for_backward(mean)
+            return chain.t["reward"].clone()
+        w, reduce_max, ag_size = chain.collision
+        c, arg = hip.collision_reward_fwd(chain.t["pred_pose"], chain.t["pred_valid"], ag_size, reduce_max)
+        chain.rule_apx = _weighted_collision(c, chain.t["pred_valid"], w)
+        ctx.save_for_backward(mean, *(() if arg is None else (arg,)))
+        return chain.t["reward"] + chain.rule_apx
 
     @staticmethod
     def backward(ctx, d_reward):
-        (mean,) = ctx.saved_tensors
+        mean, *arg = ctx.saved_tensors
         chain = ctx.chain
         d_mean = torch.empty_like(mean)
-        hip.train_chain_bwd(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, d_reward.contiguous(), d_mean)
+        d_reward = d_reward.contiguous()
+        if chain.collision is None:
+            hip.train_chain_bwd(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, d_reward, d_mean)
+            return d_mean, None
+        w, reduce_max, ag_size = chain.collision
+        g = _weighted_collision(d_reward, chain.t["pred_valid"], w)  # dL/dc
+        d_pose = hip.collision_reward_bwd(chain.t["pred_pose"], chain.t["pred_valid"], ag_size, reduce_max, g, arg[0] if arg else None)
+        hip.train_chain_bwd_pose(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, d_reward, d_pose, d_mean)
         return d_mean, None
+
+
+def collision_config(wm, b):
+    """(w_collision, reduce_collsion_with_max, ag_size [n, A, 3] f32) of a module whose differentiable reward has the collision term on
+    (utils/rewards.py), else None - then nothing of the term is launched."""
+    r = getattr(wm, "diffbar_reward", None)
+    if r is None or not (r.is_enabled and r.w_collision > 0):
+        return None
+    return float(r.w_collision), bool(r.reduce_collsion_with_max), b["ref/ag_size"].float().contiguous()
+
+
+def _weighted_collision(x: Tensor, valid: Tensor, w: float) -> Tensor:
+    """-w x on valid predictions, 0 elsewhere: the unweighted term -> r_traffic_rule_approx (rewards.py:81-82), and dL/d(reward) -> dL/dc."""
+    return (x * (-w)).masked_fill_(~valid.bool(), 0.0)
+
+
+class CollisionRewardFn(torch.autograd.Function):
+    """c [n, T, A] = the unweighted collision term of a pose log (tbx_collision_reward_fwd) from pose [n, T, A, 3] / valid [n, T, A] views
+    of any strides - the training chain's log or a permuted agent-major one - and ag_size [n, A, 3]; backward =
+    tbx_collision_reward_bwd (d_pose for x, y, yaw; no gradient for the sizes)."""
+
+    @staticmethod
+    def forward(ctx, pose, valid, ag_size, reduce_with_max):
+        valid = valid if valid.dtype == torch.uint8 else valid.to(torch.uint8)
+        c, arg = hip.collision_reward_fwd(pose, valid, ag_size, reduce_with_max)
+        ctx.save_for_backward(pose, valid, ag_size, *(() if arg is None else (arg,)))
+        ctx.reduce_with_max = reduce_with_max
+        return c
+
+    @staticmethod
+    def backward(ctx, g):
+        pose, valid, ag_size, *arg = ctx.saved_tensors
+        return hip.collision_reward_bwd(pose, valid, ag_size, ctx.reduce_with_max, g.contiguous(), arg[0] if arg else None), None, None, None

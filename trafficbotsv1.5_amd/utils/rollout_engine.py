@@ -46,6 +46,22 @@ def _scheduled(fn):
     return wrapped
 
 
+def add_collision_term(reward: Dict[str, Tensor], pred_valid: Tensor, pred_pose: Tensor, ag_size: Tensor, w_collision: float,
+                       reduce_with_max: bool) -> None:
+    """The collision term of the differentiable reward (rewards.py:76-83, w_collision > 0) into a finished log's reward dict, in place:
+    ONE tbx_collision_reward_fwd launch over the agent-major log pred_valid [n, A, T] (u8 / bool), pred_pose [n, A, T, 3] - read where
+    it lies - with ag_size [n, A, 3]. r_traffic_rule_approx = -w c on valid predictions, added into diffbar_reward;
+    diffbar_reward_valid becomes the prediction's validity (the imitation terms keep their own mask: they are 0 outside it)."""
+    n, A, T = pred_valid.shape
+    c = torch.empty(n, A, T, dtype=torch.float32, device=pred_pose.device)
+    hip.collision_reward_fwd(pred_pose.permute(0, 2, 1, 3), pred_valid.permute(0, 2, 1), ag_size.float().contiguous(), bool(reduce_with_max),
+                             out=c.permute(0, 2, 1), want_arg=False)
+    valid = pred_valid if pred_valid.dtype == torch.bool else pred_valid.view(torch.bool)
+    reward["r_traffic_rule_approx"] = c.mul_(-float(w_collision)).masked_fill_(~valid, 0.0)
+    reward["diffbar_reward"] = reward["diffbar_reward"] + reward["r_traffic_rule_approx"]
+    reward["diffbar_reward_valid"] = valid
+
+
 def lights_per_scene(tl_tokens: Dict[str, Tensor], k: int) -> Dict[str, Tensor]:
     """Per-scene view of traffic-light tokens that were expanded per rollout (`encode_scene(n_rollout=k)`: every per-light
     tensor repeated k times along the batch, map targets indexed per scene through mp_batch_div = k): entry 0 of every group
@@ -695,10 +711,12 @@ class RolloutEngine:
             lp = lp.unsqueeze(-1)
         return lp * valid_u8.to(lp.dtype)
 
-    def buffer(self, step_current: int = 10, rule_checker=None) -> RolloutBuffer:
+    def buffer(self, step_current: int = 10, rule_checker=None, collision=None) -> RolloutBuffer:
         """The rollout log as the reference's RolloutBuffer. With a TrafficRuleChecker, the five metric-only rule checks
         (collided, collided_wosac, run_road_edge, run_red_light, passive: waymo_motion.py:250 in the reference's loop) are
-        evaluated here for all steps at once from the device-resident log (tbx_rule_check over n x T frames)."""
+        evaluated here for all steps at once from the device-resident log (tbx_rule_check over n x T frames).
+        collision = (w_collision, reduce_with_max, ag_size [n, A, 3]) of a reward with w_collision > 0: the term that couples the agents
+        is computed here from the finished pose log, one launch (add_collision_term); None: no launch, the term's log is zeros."""
         S, buf = self.S, RolloutBuffer(self.T, step_current)
         if getattr(self, "tl_share_ok", None) is not None:
             ok, self.tl_share_ok = self.tl_share_ok, None
@@ -730,6 +748,8 @@ class RolloutEngine:
         buf.diffbar_reward = {"diffbar_reward_valid": b8(S["out_reward_valid"]), "diffbar_reward": r[..., 3],
                               "r_imitation_pos": r[..., 0], "r_imitation_rot": r[..., 1], "r_imitation_spd": r[..., 2],
                               "r_traffic_rule_approx": torch.zeros_like(r[..., 0])}
+        if collision is not None:
+            add_collision_term(buf.diffbar_reward, S["out_valid"], S["out_pose"], collision[2], collision[0], collision[1])
         buf.tl_state_nll = rep(S["out_tl_nll"])
         inv = self.tl_invalid_full.bool().unsqueeze(-1).expand(-1, -1, self.T).clone()
         inv[:, :, max(self.n_step_tl_gt - 1, 0):] = True  # steps past the light ground truth carry no NLL (waymo_motion.py:277-279)
