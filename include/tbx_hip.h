@@ -1067,5 +1067,6 @@ int tbx_pose_to_global(const float* xy, int ld_xy, const float* yaw, int ld_yaw,
 #include "tbx_hip_metrics.h" /* tbx_rollout_metrics */
 /* ... and the entry points of libtbx_hip_reward.so, a library of its own built beside this one (libtbx_hip.so exports none of them): */
 #include "tbx_hip_reward.h"  /* tbx_collision_reward_fwd / _bwd, tbx_train_chain_bwd_pose */
+#include "tbx_hip_loss.h"    /* libtbx_hip_loss.so, a third library: tbx_loss_shape */
 
 #endif /* TBX_HIP_H */

@@ -12,8 +12,10 @@ _lib = None
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "csrc" / "libtbx_hip.so"
 REWARD_LIB_PATH = _PKG / "csrc" / "libtbx_hip_reward.so"  # the entry points of include/tbx_hip_reward.h: a library of their own
+LOSS_LIB_PATH = _PKG / "csrc" / "libtbx_hip_loss.so"  # the entry point of include/tbx_hip_loss.h: a third library
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
 REWARD_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_reward.h"
+LOSS_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_loss.h"
 EXTENSION_HEADER_PATHS = (HEADER_PATH.parent / "tbx_hip_metrics.h",)  # included by tbx_hip.h: entry points added after ABI 7 was laid down
 
 # ---- constants mirrored from include/tbx_hip.h
@@ -204,9 +206,19 @@ class RuleCtx(C.Structure):
                 + [(n, C.c_void_p) for n in ("seg_start", "seg_grid", "lane_start", "lane_grid")])
 
 
+class LossShape(C.Structure):
+    """tbx_loss_shape_t (include/tbx_hip_loss.h). Filled by hip_train.loss_shape."""
+    _fields_ = ([(n, C.c_void_p) for n in ("pred_valid", "tf", "reward_valid", "reward", "relevant", "pick", "any_valid", "w_agent", "w", "acc",
+                                           "partials")] + [("rows", C.c_int64)]
+                + [(n, C.c_int64 * 3) for n in ("pred_valid_stride", "tf_stride", "reward_valid_stride", "reward_stride", "w_stride")]
+                + [(n, C.c_int32) for n in ("n_ag", "n_step", "step_training_start", "loss_for_teacher_forcing", "mask_irrelevant", "pad_")]
+                + [("w_relevant", C.c_float), ("discount", C.c_float)])
+
+
 RULE_COLLIDED, RULE_COLLIDED_WOSAC, RULE_RUN_ROAD_EDGE, RULE_RUN_RED_LIGHT, RULE_PASSIVE = 1, 2, 4, 8, 16
 COLLISION_MAX_AG, COLLISION_LANES = 512, 4  # TBX_COLLISION_* of include/tbx_hip_reward.h: the collision kernels' agent cap / lanes per agent
 METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
+LOSS_PARTIALS = 512  # TBX_LOSS_PARTIALS of include/tbx_hip_loss.h: tbx_loss_shape's float64 workspace
 
 _lib = None
 
@@ -261,6 +273,37 @@ def load_reward():
     for s in reward_symbols():
         getattr(lib, s).restype = C.c_int
     _reward_lib = lib
+    return lib
+
+
+def loss_symbols() -> List[str]:
+    """Entry points declared in include/tbx_hip_loss.h: what libtbx_hip_loss.so exports."""
+    return sorted(set(re.findall(_DECL, LOSS_HEADER_PATH.read_text(), flags=re.M)))
+
+
+_loss_lib = None
+
+
+def load_loss():
+    """dlopen the in-tree libtbx_hip_loss.so (tbx_loss_shape: the loss shaping of the training objective) and check it exports every symbol
+    its header declares. No GPU needed. A missing library is an error: there is no fallback path."""
+    global _loss_lib
+    if _loss_lib is not None:
+        return _loss_lib
+    load()  # (the error strings / ABI version check of the main library)
+    if not LOSS_LIB_PATH.exists():
+        raise ImportError(f"{LOSS_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`. There is no fallback path.")
+    lib = C.CDLL(str(LOSS_LIB_PATH))
+    for s in loss_symbols():
+        if not hasattr(lib, s):
+            raise ImportError(f"libtbx_hip_loss.so does not export {s}")
+    lib.tbx_loss_shape.argtypes = [C.POINTER(LossShape), C.c_void_p]
+    untyped = [s for s in loss_symbols() if getattr(lib, s).argtypes is None]
+    if untyped:
+        raise ImportError(f"abi.load_loss(): no argtypes for {untyped}")
+    for s in loss_symbols():
+        getattr(lib, s).restype = C.c_int
+    _loss_lib = lib
     return lib
 
 

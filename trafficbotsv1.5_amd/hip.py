@@ -458,3 +458,51 @@ def sim_step(state: SimState, parts: int = SIM_AGENTS | SIM_LIGHTS | SIM_ADVANCE
     _check(load().tbx_sim_step(C.byref(state), parts, rows, stream_ptr()), "tbx_sim_step")
 
 
+
+
+def _flag8(t: Optional[torch.Tensor], shape, what: str) -> Optional[torch.Tensor]:
+    """A 0/1 byte tensor (u8 or bool storage) of the given shape, on the device, as it lies."""
+    if t is None:
+        return None
+    if t.dtype not in (torch.uint8, torch.bool) or tuple(t.shape) != tuple(shape):
+        raise TypeError(f"loss_shape: {what} must be u8 / bool {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def loss_shape(pred_valid, tf, step_training_start: int, loss_for_teacher_forcing: bool, reward=None, reward_valid=None, relevant=None,
+               pick=None, mask_irrelevant: bool = False, w_relevant: float = 0.0, discount: float = -1.0, want_w: bool = False, acc=None,
+               partials=None):
+    """tbx_loss_shape (libtbx_hip_loss.so) on [rows, A, T] VIEWS of any strides - the training chain's permuted [n, T, A] log, a buffer's
+    [rows, A, T], a time slice of the engine's log: read in place. pred_valid / tf / reward_valid u8 or bool, reward f32; relevant / pick
+    [rows, A] u8 or bool, contiguous. -> (any_valid u8 [rows, A], w_agent f32 [rows, A], w f32 [rows, A, T] | None, acc f64 [2] | None):
+    acc[0] = the shaped reward sum, acc[1] = #rv, ADDED to `acc` if one is passed (else to zeros); without reward: masks only."""
+    rows, A, T = pred_valid.shape
+    dev = pred_valid.device
+    _flag8(pred_valid, (rows, A, T), "pred_valid"), _flag8(tf, (rows, A, T), "tf"), _flag8(reward_valid, (rows, A, T), "reward_valid")
+    _flag8(relevant, (rows, A), "relevant"), _flag8(pick, (rows, A), "pick")
+    if reward is not None and (reward.dtype != torch.float32 or tuple(reward.shape) != (rows, A, T)):
+        raise TypeError(f"loss_shape: reward must be f32 {(rows, A, T)}")
+    a = LossShape()
+    a.pred_valid, a.tf, a.reward_valid, a.reward = _ptr(pred_valid), _ptr(tf), _ptr(reward_valid), _ptr(reward, torch.float32)
+    a.relevant, a.pick = _cptr(relevant), _cptr(pick)
+    any_valid = torch.empty(rows, A, dtype=torch.uint8, device=dev)
+    w_agent = torch.empty(rows, A, dtype=torch.float32, device=dev)
+    w = torch.empty_like(reward) if (want_w and reward is not None) else None  # (the reward's own layout where that is dense)
+    if reward is not None:
+        acc = torch.zeros(2, dtype=torch.float64, device=dev) if acc is None else acc
+        partials = torch.empty(LOSS_PARTIALS, dtype=torch.float64, device=dev) if partials is None else partials
+        if acc.numel() < 2 or partials.numel() < LOSS_PARTIALS:
+            raise RuntimeError("loss_shape: acc needs 2, partials LOSS_PARTIALS float64 values")
+    else:
+        acc = partials = None
+    a.any_valid, a.w_agent, a.w = _ptr(any_valid), _ptr(w_agent), _ptr(w)
+    a.acc, a.partials = _cptr(acc, torch.float64), _cptr(partials, torch.float64)
+    a.rows = rows
+    for name, t in (("pred_valid", pred_valid), ("tf", tf), ("reward_valid", reward_valid), ("reward", reward), ("w", w)):
+        if t is not None:
+            setattr(a, name + "_stride", (C.c_int64 * 3)(*t.stride()))
+    a.n_ag, a.n_step, a.step_training_start = A, T, int(step_training_start)
+    a.loss_for_teacher_forcing, a.mask_irrelevant = int(bool(loss_for_teacher_forcing)), int(bool(mask_irrelevant))
+    a.w_relevant, a.discount = float(w_relevant), float(discount)
+    _check(load_loss().tbx_loss_shape(C.byref(a), stream_ptr()), "tbx_loss_shape")
+    return any_valid, w_agent, w, acc

@@ -666,10 +666,71 @@ def training_rollout_batched(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, 
                             policy=lambda step, hist, v, p, nv: (mean[:, step - 1], logits[:, step - 1]))
 
 
+def loss_shaping(cfg):
+    """(mask_irrelevant, p_loss_for_irrelevant, w_relevant_agent, temporal_discount) of a training_metrics section if any of the three
+    loss-shaping switches is on (metrics/training.py:92,104,130), else None: the default configuration launches nothing new."""
+    p = float(getattr(cfg, "p_loss_for_irrelevant", 1.0))
+    w, d = float(getattr(cfg, "w_relevant_agent", 0.0)), float(getattr(cfg, "temporal_discount", -1.0))
+    return (p < 1.0, p, w, d) if (p < 1.0 or w > 0 or d > 0) else None
+
+
+def shaped_reward(cfg, pred_valid, tf, reward, reward_valid, ag_role, pick=None):
+    """tbx_loss_shape on a rollout log's [n, A, T] views (any strides) under cfg's switches -> (shaped reward sum, #rv int64, any_valid
+    bool [n, A], w_agent f32 [n, A] or None with w_relevant_agent off). pick: the Bernoulli(p_loss_for_irrelevant) draw per (scene, agent),
+    bool [n, A]; None: drawn here on the log's device, where the reference draws it (training.py:95)."""
+    mask_irrelevant, p, w_rel, discount = loss_shaping(cfg)
+    relevant = None
+    if mask_irrelevant or w_rel > 0:
+        if ag_role is None:
+            raise ValueError("p_loss_for_irrelevant < 1 / w_relevant_agent > 0 need ag_role [n_sc, n_ag, 3]")
+        relevant = ag_role.any(-1).contiguous()
+    if not (mask_irrelevant and p > 0.0):
+        pick = None
+    elif pick is None:
+        pick = torch.bernoulli(torch.full(relevant.shape, p, device=relevant.device)).bool()
+    if reward is None:  # the masks only (a TrainingMetrics without the reward term)
+        any_valid, w_agent, _, _ = hip.loss_shape(pred_valid, tf, int(cfg.step_training_start), bool(cfg.loss_for_teacher_forcing), relevant=relevant,
+                                                  pick=pick, mask_irrelevant=mask_irrelevant, w_relevant=w_rel)
+        return None, None, any_valid.bool(), (w_agent if w_rel > 0 else None)
+    total, n_rv, any_valid, w_agent = ShapedRewardFn.apply(reward, pred_valid, tf, reward_valid, relevant, pick, int(cfg.step_training_start),
+                                                           bool(cfg.loss_for_teacher_forcing), mask_irrelevant, w_rel, discount)
+    return total, n_rv, any_valid, (w_agent if w_rel > 0 else None)
+
+
+def _training_loss_shaped(cfg, ro, navi_pred, navi_gt, post, prior, counts, ag_role, pick) -> Dict[str, Tensor]:
+    """training_loss with a loss-shaping switch on: the masks, the agent weight and the discounted reward sum come from ONE tbx_loss_shape
+    call on the log where it lies; the KL and navigation terms carry w_agent per agent, every counter stays unweighted
+    (training.py:115-120,147-153)."""
+    cnt = lambda m: m.sum().clamp(min=1)
+    total, n_rv, any_valid, w_agent = shaped_reward(cfg, ro["pred_valid"], ro["tf"], ro["reward"], ro["reward_valid"], ag_role, pick)
+    weighted = (lambda e: e) if w_agent is None else (lambda e: e * w_agent)
+    P, Q = post.distribution, prior.distribution
+    dP = Independent(Normal(P.base_dist.loc.detach(), P.base_dist.scale.detach(), validate_args=False), 1, validate_args=False)
+    dQ = Independent(Normal(Q.base_dist.loc.detach(), Q.base_dist.scale.detach(), validate_args=False), 1, validate_args=False)
+    e0 = torch.clamp(kl_divergence(dP, Q), min=cfg.kl_free_nats)
+    e1 = torch.clamp(kl_divergence(P, dQ), min=cfg.kl_free_nats)
+    kv = (post.valid if cfg.kl_for_unseen_agent else prior.valid) & any_valid
+    vae_kl = cfg.w_vae_kl * weighted(e0 + cfg.kl_balance_scale * e1).masked_fill(~kv, 0).sum() / cnt(kv)
+    reward = cfg.w_diffbar_reward * total / n_rv.clamp(min=1)
+    nv = navi_pred.valid & any_valid
+    navi = cfg.w_navi * weighted(-navi_pred.log_prob(navi_gt)).masked_fill(~nv, 0).sum() / cnt(nv)
+    tv = ~ro["tl_nll_invalid"]
+    tl = cfg.w_tl_state * ro["tl_nll"].masked_fill(~tv, 0).sum() / cnt(tv)
+    if counts is not None:
+        counts.update(vae_kl=kv.sum(), diffbar_reward=n_rv, navi_loss=nv.sum(), tl_state_loss=tv.sum())
+    out = {"loss": vae_kl - reward + navi + tl, "vae_kl": vae_kl, "diffbar_reward": reward, "navi_loss": navi, "tl_state_loss": tl}
+    if "rule_apx" in ro:
+        out["dr_rule_apx"] = ro["rule_apx"].detach().sum() / n_rv.clamp(min=1)
+    return out
+
+
 def training_loss(cfg, ro, navi_pred: DestCategorical, navi_gt, post: DiagGaussian, prior: DiagGaussian,
-                  counts: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
-    """metrics/training.py:74-189 + metrics/loss.py:39-77 (default weights / switches). counts: receives every term's normaliser
-    (the number of entries its sum runs over, un-clamped) - a term of a batch is the count-weighted mean of its per-scene terms."""
+                  counts: Optional[Dict[str, Tensor]] = None, ag_role: Optional[Tensor] = None, pick: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """metrics/training.py:74-189 + metrics/loss.py:39-77. counts: receives every term's normaliser (the number of entries its sum runs
+    over, un-clamped and unweighted) - a term of a batch is the count-weighted mean of its per-scene terms. ag_role [n, A, 3] / pick
+    [n, A] bool are read only with a loss-shaping switch on (loss_shaping; then the log must be on the device: tbx_loss_shape)."""
+    if loss_shaping(cfg) is not None:
+        return _training_loss_shaped(cfg, ro, navi_pred, navi_gt, post, prior, counts, ag_role, pick)
     # A term whose counter is zero (a batch without a valid light / agent) is left out by the reference (training.py:166-186:
     # `if counter > 0`): sum = 0 over a count clamped to 1 gives that 0 without a host branch (the step stays capturable).
     cnt = lambda m: m.sum().clamp(min=1)
@@ -778,4 +839,7 @@ def _training_step(wm, raw_batch, noise, use_prior) -> Dict[str, Tensor]:
     rollout = training_rollout_batched if getattr(wm, "time_batched_training", True) else training_rollout
     ro = rollout(wm, b, mp, tl_tokens, z, l_valid, tf.ag_teacher_forcing, hp.time_step_end)
     wm.last_counts = {}
-    return training_loss(hp.training_metrics, ro, navi_pred, b["gt/ag_navi"], post, prior, counts=wm.last_counts)
+    # (ag_role and the pick are read only with a loss-shaping switch on. wm.loss_irrelevant_pick, a [n, A] bool tensor in the manner of
+    # wm.attn_dropout_seed: the draw of p_loss_for_irrelevant, read in place - by every replay of a captured step - instead of drawn)
+    return training_loss(hp.training_metrics, ro, navi_pred, b["gt/ag_navi"], post, prior, counts=wm.last_counts, ag_role=b.get("ref/ag_role"),
+                         pick=getattr(wm, "loss_irrelevant_pick", None))

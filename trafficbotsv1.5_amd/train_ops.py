@@ -779,3 +779,25 @@ class CollisionRewardFn(torch.autograd.Function):
     def backward(ctx, g):
         pose, valid, ag_size, *arg = ctx.saved_tensors
         return hip.collision_reward_bwd(pose, valid, ag_size, ctx.reduce_with_max, g.contiguous(), arg[0] if arg else None), None, None, None
+
+
+class ShapedRewardFn(torch.autograd.Function):
+    """The training objective's loss shaping (metrics/training.py:90-138: p_loss_for_irrelevant, w_relevant_agent, temporal_discount) of a
+    finished rollout log, one tbx_loss_shape call on [rows, A, T] views read where they lie: (shaped reward sum f32, #rv int64,
+    any_valid bool [rows, A], w_agent f32 [rows, A]). backward: d_reward = g * w, one elementwise product in the log's own layout."""
+
+    @staticmethod
+    def forward(ctx, reward, pred_valid, tf, reward_valid, relevant, pick, step_training_start, loss_for_teacher_forcing, mask_irrelevant,
+                w_relevant, discount):
+        any_valid, w_agent, w, acc = hip.loss_shape(pred_valid, tf, step_training_start, loss_for_teacher_forcing, reward=reward.detach(),
+                                                    reward_valid=reward_valid, relevant=relevant, pick=pick, mask_irrelevant=mask_irrelevant,
+                                                    w_relevant=w_relevant, discount=discount, want_w=True)
+        ctx.save_for_backward(w)
+        total, count, any_valid = acc[0].float(), acc[1].long(), any_valid.bool()
+        ctx.mark_non_differentiable(count, any_valid, w_agent)
+        return total, count, any_valid, w_agent
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (w,) = ctx.saved_tensors
+        return (g * w,) + (None,) * 10
