@@ -1068,5 +1068,6 @@ int tbx_pose_to_global(const float* xy, int ld_xy, const float* yaw, int ld_yaw,
 /* ... and the entry points of libtbx_hip_reward.so, a library of its own built beside this one (libtbx_hip.so exports none of them): */
 #include "tbx_hip_reward.h"  /* tbx_collision_reward_fwd / _bwd, tbx_train_chain_bwd_pose */
 #include "tbx_hip_loss.h"    /* libtbx_hip_loss.so, a third library: tbx_loss_shape */
+#include "tbx_hip_tf.h"      /* libtbx_hip_tf.so, a fourth library: tbx_tf_threshold */
 
 #endif /* TBX_HIP_H */

@@ -16,6 +16,8 @@ LOSS_LIB_PATH = _PKG / "csrc" / "libtbx_hip_loss.so"  # the entry point of inclu
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
 REWARD_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_reward.h"
 LOSS_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_loss.h"
+TF_LIB_PATH = _PKG / "csrc" / "libtbx_hip_tf.so"  # the entry point of include/tbx_hip_tf.h: a fourth library
+TF_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_tf.h"
 EXTENSION_HEADER_PATHS = (HEADER_PATH.parent / "tbx_hip_metrics.h",)  # included by tbx_hip.h: entry points added after ABI 7 was laid down
 
 # ---- constants mirrored from include/tbx_hip.h
@@ -215,6 +217,13 @@ class LossShape(C.Structure):
                 + [("w_relevant", C.c_float), ("discount", C.c_float)])
 
 
+class TfThreshold(C.Structure):
+    """tbx_tf_threshold_t (include/tbx_hip_tf.h). Filled by hip.tf_threshold."""
+    _fields_ = ([(n, C.c_void_p) for n in ("step_dev", "valid", "pose", "motion", "gt_valid", "gt_pose", "gt_motion", "tf_mask", "out_reset")]
+                + [("n_rows", C.c_int64)] + [(n, C.c_int32) for n in ("n_ag", "n_step_gt", "step_host", "pad_")]
+                + [(n, C.c_float) for n in ("threshold_xy", "threshold_yaw", "threshold_spd", "pad2_")])
+
+
 RULE_COLLIDED, RULE_COLLIDED_WOSAC, RULE_RUN_ROAD_EDGE, RULE_RUN_RED_LIGHT, RULE_PASSIVE = 1, 2, 4, 8, 16
 COLLISION_MAX_AG, COLLISION_LANES = 512, 4  # TBX_COLLISION_* of include/tbx_hip_reward.h: the collision kernels' agent cap / lanes per agent
 METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
@@ -304,6 +313,37 @@ def load_loss():
     for s in loss_symbols():
         getattr(lib, s).restype = C.c_int
     _loss_lib = lib
+    return lib
+
+
+def tf_symbols() -> List[str]:
+    """Entry points declared in include/tbx_hip_tf.h: what libtbx_hip_tf.so exports."""
+    return sorted(set(re.findall(_DECL, TF_HEADER_PATH.read_text(), flags=re.M)))
+
+
+_tf_lib = None
+
+
+def load_tf():
+    """dlopen the in-tree libtbx_hip_tf.so (tbx_tf_threshold: the error-threshold resets of teacher forcing) and check it exports every
+    symbol its header declares. No GPU needed. A missing library is an error: there is no fallback path."""
+    global _tf_lib
+    if _tf_lib is not None:
+        return _tf_lib
+    load()  # (the error strings / ABI version check of the main library)
+    if not TF_LIB_PATH.exists():
+        raise ImportError(f"{TF_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`. There is no fallback path.")
+    lib = C.CDLL(str(TF_LIB_PATH))
+    for s in tf_symbols():
+        if not hasattr(lib, s):
+            raise ImportError(f"libtbx_hip_tf.so does not export {s}")
+    lib.tbx_tf_threshold.argtypes = [C.POINTER(TfThreshold), C.c_void_p]
+    untyped = [s for s in tf_symbols() if getattr(lib, s).argtypes is None]
+    if untyped:
+        raise ImportError(f"abi.load_tf(): no argtypes for {untyped}")
+    for s in tf_symbols():
+        getattr(lib, s).restype = C.c_int
+    _tf_lib = lib
     return lib
 
 

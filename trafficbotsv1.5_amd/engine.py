@@ -103,7 +103,9 @@ class Schedule:
     # queue - the lights' and the agents' tbx_front as one launch (tbx_front_pair), their layer l as one launch (tbx_knarpe_dec_layer_pair),
     # the lights' tbx_sim_step in the tail of their last layer (tbx_tl_tail_t.sim_state) as the agents' is (fused_tail): 5 launches per
     # step and no cross-queue edge (the join of the two-stream form costs ~8 us per step: DESIGN.md 8.1). Same launches' arithmetic:
-    # bit-identical rollouts (tests/test_hip_rollout.py).
+    # bit-identical rollouts (tests/test_hip_rollout.py). (An engine built for a TeacherForcing with an error threshold on puts a sixth
+    # launch, tbx_tf_threshold, at the head of the step - on the agents' stream in the two-stream form; no Schedule field: it is a
+    # property of the rollout's TeacherForcing, RolloutEngine(tf_thresholds=).)
     one_queue: bool = True
     # steps per multi-step graph (even; 1: off). A replay boundary costs a few us of idle device: 4 -> 197.9 k, 16 -> 199.4 k, 40 ->
     # 200.4 k agent-steps/s at the 64-agent scene. Capturing g steps costs g eager steps of host time, so the default suits an engine

@@ -460,12 +460,12 @@ def sim_step(state: SimState, parts: int = SIM_AGENTS | SIM_LIGHTS | SIM_ADVANCE
 
 
 
-def _flag8(t: Optional[torch.Tensor], shape, what: str) -> Optional[torch.Tensor]:
+def _flag8(t: Optional[torch.Tensor], shape, what: str, who: str = "loss_shape") -> Optional[torch.Tensor]:
     """A 0/1 byte tensor (u8 or bool storage) of the given shape, on the device, as it lies."""
     if t is None:
         return None
     if t.dtype not in (torch.uint8, torch.bool) or tuple(t.shape) != tuple(shape):
-        raise TypeError(f"loss_shape: {what} must be u8 / bool {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+        raise TypeError(f"{who}: {what} must be u8 / bool {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
     return t
 
 
@@ -506,3 +506,38 @@ def loss_shape(pred_valid, tf, step_training_start: int, loss_for_teacher_forcin
     a.w_relevant, a.discount = float(w_relevant), float(discount)
     _check(load_loss().tbx_loss_shape(C.byref(a), stream_ptr()), "tbx_loss_shape")
     return any_valid, w_agent, w, acc
+
+
+def tf_threshold_args(thresholds, step, valid, pose, motion, gt_valid, gt_pose, gt_motion, tf_mask, out_reset=None) -> "TfThreshold":
+    """tbx_tf_threshold_t over the caller's tensors, as they lie (all contiguous; 0/1 bytes as u8 or bool): thresholds = (xy [m], yaw
+    [deg], spd [m/s]), <= 0 is off; step an int (step_host) or an int32 device tensor whose first word is the 1-based step about to run
+    (step_dev: the word tbx_sim_state_t.step points to). The struct holds pointers only: the caller keeps the tensors alive."""
+    rows, A, Tg = gt_valid.shape
+    for name, t, shape in (("valid", valid, (rows, A)), ("gt_valid", gt_valid, (rows, A, Tg)), ("tf_mask", tf_mask, (rows, A, Tg)),
+                           ("out_reset", out_reset, (rows, A))):
+        _flag8(t, shape, name, who="tf_threshold")
+    for name, t, shape in (("pose", pose, (rows, A, 3)), ("motion", motion, (rows, A, 3)), ("gt_pose", gt_pose, (rows, A, Tg, 3)),
+                           ("gt_motion", gt_motion, (rows, A, Tg, 3))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise TypeError(f"tf_threshold: {name} must be f32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    a = TfThreshold()
+    a.valid, a.pose, a.motion = _cptr(valid), _cptr(pose), _cptr(motion)
+    a.gt_valid, a.gt_pose, a.gt_motion = _cptr(gt_valid), _cptr(gt_pose), _cptr(gt_motion)
+    a.tf_mask, a.out_reset = _cptr(tf_mask), _cptr(out_reset)
+    if torch.is_tensor(step):
+        a.step_dev, a.step_host = _cptr(step, torch.int32), 0
+    else:
+        a.step_dev, a.step_host = None, int(step)
+    a.n_rows, a.n_ag, a.n_step_gt = rows, A, Tg
+    a.threshold_xy, a.threshold_yaw, a.threshold_spd = (float(t) for t in thresholds)
+    return a
+
+
+def tf_threshold_launch(a: "TfThreshold") -> None:
+    """tbx_tf_threshold (libtbx_hip_tf.so) on the current stream: one step's error-threshold resets ORed into column s of a.tf_mask."""
+    _check(load_tf().tbx_tf_threshold(C.byref(a), stream_ptr()), "tbx_tf_threshold")
+
+
+def tf_threshold(thresholds, step, valid, pose, motion, gt_valid, gt_pose, gt_motion, tf_mask, out_reset=None) -> None:
+    """tf_threshold_args + tf_threshold_launch: utils/teacher_forcing.py:131-145 for one step, in place on tf_mask [rows, A, Tg]."""
+    tf_threshold_launch(tf_threshold_args(thresholds, step, valid, pose, motion, gt_valid, gt_pose, gt_motion, tf_mask, out_reset))

@@ -258,7 +258,9 @@ class GraphedTrainStep:
     buffers, refill the random inputs, replay, then (eagerly, outside the graph) the flat gradient all-reduce over
     RCCL, the clip and the optimizer step - the exchange keeps its own place between backward and update, as in
     `train_step`. Device-side generators (dropout, teacher-forcing Bernoulli draws) advance per replay through
-    torch's graph-safe Philox offsets.
+    torch's graph-safe Philox offsets. Error-threshold teacher forcing (TeacherForcing.has_threshold) is captured as it runs: the
+    tbx_tf_threshold launch before every step of the stepping pass, on a table that TeacherForcing.init rebuilds inside every replay, so
+    a replay never starts from the previous replay's resets.
 
     Re-capture when the epoch changes (TeacherForcing's schedules read `current_epoch` on the host).
 

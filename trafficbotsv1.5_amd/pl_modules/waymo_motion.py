@@ -160,11 +160,14 @@ class WaymoMotion(LightningModule):
                   map_pos=rule_checker.mp_pos, map_dir=rule_checker.mp_dir, map_boundary=rule_checker.mp_boundary,
                   n_step=step_end, reward_weights=(rc.l_pos.weight, rc.l_rot.weight, rc.l_spd.weight),
                   ag_navi_log_prob=ag_tokens.get("ag_navi_log_prob"), stepwise=stepwise)
-        eng = self._engine_for(kw, dev, sample_actions=not deterministic_action)
+        # error thresholds: the engine's own loop decides the resets on the device, one launch per step (a step-wise engine is handed
+        # overrides that TeacherForcing.get has already decided)
+        thr = teacher_forcing.thresholds if teacher_forcing.has_threshold and not stepwise else None
+        eng = self._engine_for(kw, dev, sample_actions=not deterministic_action, tf_thresholds=thr)
         self.dynamics.bind(eng)
         return eng
 
-    def _engine_for(self, kw: dict, dev, sample_actions: bool = False) -> RolloutEngine:
+    def _engine_for(self, kw: dict, dev, sample_actions: bool = False, tf_thresholds=None) -> RolloutEngine:
         """One engine per (shapes, schedule, sampled / deterministic actions, weights), refilled in place: a loop over scenes (validation_step, waymo_motion.py:526)
         captures its hipGraphs once. `engine_cache = 0` turns the cache off (a fresh engine per rollout). kw: RolloutEngine.reset's."""
         mp_tokens, tl_tokens = kw["mp_tokens"], kw["tl_tokens"]
@@ -172,12 +175,14 @@ class WaymoMotion(LightningModule):
         # (weights: every parameter's storage AND version - an optimizer step, load_state_dict, .to() or `p.data = ` all change one)
         key = (RolloutEngine.shape_key(**kw), dataclasses.astuple(sched), str(dev), self.training, bool(sample_actions),
                hash(weights_stamp(self.model.parameters())))
+        if tf_thresholds is not None:  # (off: the key, the engine and its graphs are the ones without the feature)
+            key += (tuple(tf_thresholds),)
         eng = self._engines.get(key) if self.engine_cache > 0 else None
         if eng is not None:
             eng.refill(**kw)
             self._engines.move_to_end(key)
         else:
-            eng = RolloutEngine(self.model, self.dynamics, dev, schedule=sched, sample_actions=sample_actions)
+            eng = RolloutEngine(self.model, self.dynamics, dev, schedule=sched, sample_actions=sample_actions, tf_thresholds=tf_thresholds)
             if self.engine_cache > 0:
                 # a cached engine is refilled in place with later scenes: it owns COPIES of the first scene's token dicts (one copy
                 # per engine, not per rollout), so a caller still holding encode_scene()'s output never sees it change

@@ -39,6 +39,7 @@ from .hip import Seg
 from .models.modules.distributions import DestCategorical, DiagGaussian
 from .train_ops import *  # noqa: F401,F403  (autograd Functions + linear / layer_norm / residual / mlp / pointnet / attention helpers)
 from .train_ops import _attn_residual, _drop, _drop_args, _glue_ok, _pointnet_fused_ok  # noqa: F401
+from .utils.teacher_forcing import threshold_resets
 from .train_state import (ATTN_MFMA_MIN_ROWS, HEADS_TILE, TALL_LINEAR, WGRAD_MIN_ROWS, _DropScope, _POLICY_SITE0, bf16_contractions,  # noqa: F401
                           module_scope, precision)
 
@@ -386,13 +387,17 @@ def _bits(one_hot: Tensor) -> Tensor:
 
 
 def training_rollout(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, step_end: int, policy=None, record: Optional[dict] = None,
-                     need_hist: bool = True) -> Dict[str, Tensor]:
+                     need_hist: bool = True, tf_thresholds=None) -> Dict[str, Tensor]:
     """Closed-loop training rollout (waymo_motion.py:206-311 with training=True: model inputs detached, the only
     cross-step gradient path is the dynamics chain). The per-step state machine is elementwise torch on [n,A] tensors
     (it needs autograd); rule feedback = outside-map + dest-reached as in tbx_sim_step.
     policy(step, hist, valid, pose, navi_valid) -> (mean [n,A,2], logits [n,L,5]); None = policy_step with autograd, one step
     at a time (the reference's order of evaluation). record: dict of lists that receives every step's policy inputs.
-    need_hist=False: the policy does not read the windows (they are not built)."""
+    need_hist=False: the policy does not read the windows (they are not built).
+    tf_thresholds = TeacherForcing.thresholds with one of them on: THIS call decides the error-threshold resets - before every step, from
+    the state at its entry, ORed in place into tf_mask[:, :, step] (teacher_forcing.py:129-145; tbx_tf_threshold on the device) - as the
+    pass that steps does (the plain step-by-step rollout, the recording pass). None: the table is only read - the replay on batched means
+    never re-decides, it reads what the stepping pass left. The gradient stops at a reset as at any forced step."""
     model, dyn, rc = wm.model, wm.dynamics, wm.hp.differentiable_reward
     gt_valid, gt_pose, gt_motion, tl_gt = b["gt/ag_valid"], b["gt/ag_pose"], b["gt/ag_motion"], b["gt/tl_state"]
     ag_type, ag_attr6, dest = b["ref/ag_type"], b["sc/ag_attr"].float().contiguous(), b["gt/ag_navi"]
@@ -438,6 +443,8 @@ def training_rollout(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, step_end
             for k, v in (("hv", hist[0]), ("hp", hist[1]), ("hm", hist[2]), ("ht", hist[3]), ("valid", valid), ("pose", pose.detach()),
                          ("navi_valid", navi_valid)):
                 record.setdefault(k, []).append(v)
+        if tf_thresholds is not None and step < Tg:
+            decide_resets(tf_thresholds, step, valid, pose.detach(), motion.detach(), gt_valid, gt_pose, gt_motion, tf_mask)
         mean, logits = policy(step, hist, valid, pose.detach(), navi_valid)
         inv1 = ~valid.unsqueeze(-1)
         action = (torch.tanh(mean) * lim).masked_fill(inv1, 0)
@@ -502,6 +509,19 @@ def training_rollout(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, step_end
     return ro
 
 
+def decide_resets(thresholds, step: int, valid: Tensor, pose: Tensor, motion: Tensor, gt_valid: Tensor, gt_pose: Tensor, gt_motion: Tensor,
+                  tf_mask: Tensor) -> None:
+    """One step's error-threshold resets into tf_mask[:, :, step] (bool [n, A, Tg], dense), in place: one tbx_tf_threshold launch on device
+    tensors, utils/teacher_forcing.threshold_resets on the host."""
+    with torch.no_grad():
+        if not tf_mask.is_cuda:
+            tf_mask[:, :, step] |= threshold_resets(thresholds, valid, pose.float(), motion.float(), gt_valid[:, :, step - 1],
+                                                    gt_pose[:, :, step - 1].float(), gt_motion[:, :, step - 1].float())
+            return
+        hip.tf_threshold(thresholds, int(step), valid.contiguous(), pose.float().contiguous(), motion.float().contiguous(), gt_valid.contiguous(),
+                         gt_pose.float().contiguous(), gt_motion.float().contiguous(), tf_mask)
+
+
 def tl_nll_all_steps(logits: Tensor, tl_gt: Tensor, tl_invalid: Tensor):
     """The light-state NLL of every step at once (waymo_motion.py:277-283): logits [n,T,L,5] of steps 1..T, tl_gt [n,L,Tt,5] one-hot,
     -> (nll [n,L,T], invalid [n,L,T]); steps without ground truth count as invalid."""
@@ -551,10 +571,13 @@ def _kv_tables_tall(x: Tensor, norms_and_attns) -> Tensor:
     return out
 
 
-def training_rollout_batched(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, step_end: int) -> Dict[str, Tensor]:
+def training_rollout_batched(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, step_end: int, tf_thresholds=None) -> Dict[str, Tensor]:
     """The same rollout, time-batched (module docstring): a step-by-step pass without autograd that records every step's
     policy inputs, then the T policy evaluations of every scene as one differentiated batch of n x T entries in [scene][step]
-    order, then the per-step dynamics / reward chain on the batched means (the only cross-step gradient path)."""
+    order, then the per-step dynamics / reward chain on the batched means (the only cross-step gradient path).
+    tf_thresholds (error-threshold teacher forcing on): a reset is decided ONCE, in the pass that steps - tbx_tf_threshold before every
+    chain.step on the chain's own state and table, or training_rollout's recording pass - and never re-decided: the differentiated replay
+    and its reverse walk read the finished table, so the two passes take the same resets."""
     model = wm.model
     T = step_end
     n = b["gt/ag_valid"].shape[0]
@@ -641,10 +664,14 @@ def training_rollout_batched(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, 
                 # (the light windows are only read when the lights are encoded in the step: not with their tokens made ahead)
                 mean1, _ = policy1(step, (hv, hp, hm, ht_steps[:, step - 1] if tl_chunks is not None else ht_steps[:, step - 1].contiguous()),
                                    valid_, pose_, navi_valid_)
+                if tf_thresholds is not None:
+                    chain.decide(tf_thresholds, step)
                 chain.step(step, mean1)
             inputs = chain.windows()
+            if tf_thresholds is not None:  # (the TeacherForcing object's table keeps the bits, as after the reference's own loop)
+                tf_mask.copy_(chain.t["tf_mask"])
         else:
-            training_rollout(wm, b, mp1, tl1, z.detach(), z_valid, tf_mask, step_end, policy=policy1, record=rec)
+            training_rollout(wm, b, mp1, tl1, z.detach(), z_valid, tf_mask, step_end, policy=policy1, record=rec, tf_thresholds=tf_thresholds)
             st = {k: torch.stack(v, 1) for k, v in rec.items()}  # [n, T, ...]
             inputs = (flat(st["hv"]), flat(st["hp"]), flat(st["hm"]), flat(st["valid"]), flat(st["pose"]), flat(st["navi_valid"]))
     if tl_chunks is not None:
@@ -837,7 +864,10 @@ def _training_step(wm, raw_batch, noise, use_prior) -> Dict[str, Tensor]:
     tf.init(ag_valid=b["gt/ag_valid"], ag_pose=b["gt/ag_pose"], ag_motion=b["gt/ag_motion"], tl_state=b["gt/tl_state"],
             current_epoch=wm.current_epoch)
     rollout = training_rollout_batched if getattr(wm, "time_batched_training", True) else training_rollout
-    ro = rollout(wm, b, mp, tl_tokens, z, l_valid, tf.ag_teacher_forcing, hp.time_step_end)
+    if tf.has_threshold:  # (off: the call and everything behind it are the ones without the feature)
+        ro = rollout(wm, b, mp, tl_tokens, z, l_valid, tf.ag_teacher_forcing, hp.time_step_end, tf_thresholds=tf.thresholds)
+    else:
+        ro = rollout(wm, b, mp, tl_tokens, z, l_valid, tf.ag_teacher_forcing, hp.time_step_end)
     wm.last_counts = {}
     # (ag_role and the pick are read only with a loss-shaping switch on. wm.loss_irrelevant_pick, a [n, A] bool tensor in the manner of
     # wm.attn_dropout_seed: the draw of p_loss_for_irrelevant, read in place - by every replay of a captured step - instead of drawn)

@@ -686,6 +686,13 @@ class TrainChain:
         cur = s - 1 + W - 1
         return hv, hp, hm, t["rec_valid"][:, cur].bool(), t["rec_pose"][:, cur], t["rec_navi_valid"][:, cur].bool()
 
+    def decide(self, thresholds, s: int) -> None:
+        """Error-threshold teacher forcing: step s's resets into the chain's own table, from the state at entry of the step - ONE
+        tbx_tf_threshold launch before `step(s, ...)` in the stepping pass. `run_all` / TrainChainFn and the reverse walk then read the
+        finished table through the same tf_mask pointer: a reset is never re-decided."""
+        t = self.t
+        hip.tf_threshold(thresholds, int(s), t["valid"], t["pose"], t["motion"], t["gt_valid"], t["gt_pose"], t["gt_motion"], t["tf_mask"])
+
     def step(self, s: int, mean: Tensor) -> None:
         mean = mean.detach().reshape(self.n, self.A, 2).contiguous()
         self._emit_windows(mean, s - 1, s)  # the step + the next step's policy inputs in one launch

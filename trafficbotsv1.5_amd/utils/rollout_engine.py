@@ -92,13 +92,18 @@ class RolloutEngine:
             cls._streams[key] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
         return cls._streams[key]
 
-    def __init__(self, model, dynamics, device, schedule: Optional[engine.Schedule] = None, sample_actions: bool = False) -> None:
+    def __init__(self, model, dynamics, device, schedule: Optional[engine.Schedule] = None, sample_actions: bool = False,
+                 tf_thresholds: Optional[Tuple[float, float, float]] = None) -> None:
         """sample_actions: Dynamics.update_ag with deterministic=False (dynamics.py:87-90) - every step adds exp(log_std) * eps to the
         action mean inside tbx_sim_step (tbx_sim_state_t.act_seed) and logs eps and the sample's log-probability. Fixed at
         construction like the schedule: the captured graphs hold the descriptor that says so."""
         self.model, self.dyn, self.dev = model, dynamics, device
         self.sched = schedule if schedule is not None else engine.current()
         self.sample_actions = bool(sample_actions)
+        # tf_thresholds = TeacherForcing.thresholds with one of them on (else None: nothing below exists): every step of the engine's own
+        # loop starts with ONE tbx_tf_threshold launch on the agents' queue that ORs the step's resets into the engine's table before the
+        # agents' part of the step reads it. Fixed at construction: the captured graphs hold the launch and its arguments.
+        self.tf_thresholds = tuple(float(t) for t in tf_thresholds) if tf_thresholds is not None and any(t > 0 for t in tf_thresholds) else None
         self._graph_steps = 1  # steps per replay of graph_multi, fixed when it is captured
         self.reused = False    # True: kept by its owner across rollouts (refill): buffer() hands out copies of the logs
         self.graph: Optional[torch.cuda.CUDAGraph] = None
@@ -196,6 +201,11 @@ class RolloutEngine:
         init["hist_pose"][:, :, -1] = init["ag_pose"]
         init["hist_motion"][:, :, -1] = init["ag_motion"]
         init["hist_tl"][:, :, -1] = init["tl_state"]
+        self._tf_args = None
+        if self.tf_thresholds is not None and not stepwise:
+            # the table is WRITTEN during the rollout (each of the n rows decides for itself): the schedule's table is part of the pristine
+            # state, so restore() / refill() start every rollout from it and not from the last rollout's resets
+            init["tf_mask"] = S["tf_mask"]
         self.init_state = init
         for k, v in init.items():
             S[k] = v.clone()
@@ -237,6 +247,9 @@ class RolloutEngine:
                 for d in range(2):
                     st.act_log_std[ty][d] = self._act_log_std[ty][d]
         self.sim_state = st
+        if "tf_mask" in init:  # (the device step counter the agents' part of tbx_sim_step advances: one captured launch serves every step)
+            self._tf_args = hip.tf_threshold_args(self.tf_thresholds, S["step"], S["ag_valid"], S["ag_pose"], S["ag_motion"], S["gt_valid"],
+                                                  S["gt_pose"], S["gt_motion"], S["tf_mask"])
         # the lights' part of tbx_sim_step only touches the light arrays: its own descriptor with their batch size
         self.sim_state_tl = st
         if kl > 1:
@@ -291,7 +304,8 @@ class RolloutEngine:
         key = self.shape_key(**kw)
         if key != self._shape_key:
             raise ValueError("refill: shapes differ from the ones this engine was built for (use a new engine)")
-        fresh = RolloutEngine(self.model, self.dyn, self.dev, schedule=self.sched, sample_actions=self.sample_actions)
+        fresh = RolloutEngine(self.model, self.dyn, self.dev, schedule=self.sched, sample_actions=self.sample_actions,
+                              tf_thresholds=self.tf_thresholds)
         RolloutEngine.reset.__wrapped__(fresh, _lights_ahead_pass=False, _tl_div=self.tl_div, _act_log_std=getattr(self, "_act_log_std", None), **kw)
         return fresh
 
@@ -506,6 +520,7 @@ class RolloutEngine:
     def step(self) -> None:
         S, main = self.S, torch.cuda.current_stream()
         if not self.sched.lights_ahead:
+            self._tf_threshold()
             self.model.policy_step(S["hist_valid"], S["hist_pose"], S["hist_motion"], S["hist_tl"], self.ag_attr6,
                                    S["ag_type_idx"], self.ag_latent, self.latent_invalid, self.dest, S["navi_valid"],
                                    self.tl_tokens, self.mp_tokens, self.policy_out, rollout_consts=self.consts)
@@ -534,6 +549,7 @@ class RolloutEngine:
             else:
                 hip.sim_step(st_tl, parts_tl)
                 self._tl_ahead(1 - p)
+        self._tf_threshold()  # (on the agents' stream: the lights never read the table)
         fuse = early and self.sched.fused_tail
         self.model.agent_policy(S["hist_valid"], S["hist_pose"], S["hist_motion"], self.ag_attr6, S["ag_type_idx"],
                                 self.ag_latent, self.latent_invalid, self.dest, S["navi_valid"], self.tl_tokens,
@@ -555,6 +571,13 @@ class RolloutEngine:
             hip.sim_step(self.sim_state, hip.SIM_AGENTS | hip.SIM_ADVANCE)
         self.parity = 1 - p
 
+    def _tf_threshold(self) -> None:
+        """Error-threshold teacher forcing (TeacherForcing.has_threshold): this step's resets into column s of the engine's table, from the
+        state the previous step left - behind the launch that finished step s - 1 for the agents, ahead of the one that holds step s's
+        agents' part. s is read from the device counter. Without thresholds nothing is launched."""
+        if self._tf_args is not None:
+            hip.tf_threshold_launch(self._tf_args)
+
     def _step_one_queue(self) -> None:
         """One closed-loop step as FIVE launches on the stepping stream (Schedule.one_queue): the lights' pass for the NEXT agent step
         (window -> tables into the other buffer, logits, then - in its last layer's tail - the lights' own update) paired launch by
@@ -562,6 +585,7 @@ class RolloutEngine:
         of launching; the halves are independent, so pairing them changes no result."""
         S, p = self.S, self.parity
         tail = dict(sim_state=self.sim_state, parts=hip.SIM_AGENTS | hip.SIM_ADVANCE)
+        self._tf_threshold()  # (error thresholds on: a sixth launch, at the head of the step)
         if not self._prep_ready:
             # the very first step of a fresh engine (no tbx_agent_prep buffers yet: _prime_prep): the same launches one after the other
             self._tl_ahead(1 - p, prepared=self._tl_prep)
