@@ -1061,13 +1061,12 @@ int tbx_pose_to_global(const float* xy, int ld_xy, const float* yaw, int ld_yaw,
 }
 #endif
 
-/* Entry points added after ABI 7 was laid down, without a change to any declaration above, are declared in extension headers that
- * this header includes - including tbx_hip.h declares everything libtbx_hip.so exports. tbx_version() stays 7: a host built against
- * the declarations above runs unchanged on a library that has the extensions. */
+/* Entry points added after ABI 7 was laid down, without a change to any declaration above, are declared in topical headers that this
+ * header includes: sections of this one ABI, all exported by libtbx_hip.so - including tbx_hip.h declares everything the library
+ * exports. tbx_version() stays 7: a host built against the declarations above runs unchanged on a library that has the additions. */
 #include "tbx_hip_metrics.h" /* tbx_rollout_metrics */
-/* ... and the entry points of libtbx_hip_reward.so, a library of its own built beside this one (libtbx_hip.so exports none of them): */
 #include "tbx_hip_reward.h"  /* tbx_collision_reward_fwd / _bwd, tbx_train_chain_bwd_pose */
-#include "tbx_hip_loss.h"    /* libtbx_hip_loss.so, a third library: tbx_loss_shape */
-#include "tbx_hip_tf.h"      /* libtbx_hip_tf.so, a fourth library: tbx_tf_threshold */
+#include "tbx_hip_loss.h"    /* tbx_loss_shape */
+#include "tbx_hip_tf.h"      /* tbx_tf_threshold */
 
 #endif /* TBX_HIP_H */

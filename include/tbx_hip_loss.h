@@ -1,10 +1,9 @@
 /*
- * libtbx_hip_loss.so - a third library beside libtbx_hip.so and libtbx_hip_reward.so, under the contract of include/tbx_hip.h (which
- * includes this header: device pointers to caller-owned buffers, nothing allocated or retained, kernels only enqueued on `stream`,
- * TBX_* return codes before any launch). libtbx_hip.so's export list stays exactly ABI 7 + tbx_rollout_metrics and libtbx_hip_reward.so's
- * its three entry points; a host that wants the entry point below links / dlopens this library as well (built by the same Makefile from
- * csrc/loss_shape.hip). It is the loss shaping of the training objective (models/metrics/training.py:90-138: temporal_discount,
- * p_loss_for_irrelevant, w_relevant_agent), a pure function of a finished rollout log.
+ * The loss section of the C ABI of include/tbx_hip.h, exported by libtbx_hip.so like every other entry point (tbx_hip.h includes this
+ * header; its contract - device pointers to caller-owned buffers, nothing allocated or retained, kernels only enqueued on `stream`,
+ * TBX_* return codes before any launch - holds here too). Source: csrc/loss_shape.hip. It is the loss shaping of the training
+ * objective (models/metrics/training.py:90-138: temporal_discount, p_loss_for_irrelevant, w_relevant_agent), a pure function of a
+ * finished rollout log.
  */
 #ifndef TBX_HIP_LOSS_H
 #define TBX_HIP_LOSS_H

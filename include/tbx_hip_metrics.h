@@ -1,7 +1,8 @@
 /*
- * libtbx_hip.so - extension of the C ABI of include/tbx_hip.h (which includes this header; its contract - device pointers to
- * caller-owned buffers, nothing allocated or retained, kernels only enqueued on `stream`, TBX_* return codes - holds here too):
- * the reduction of a device-resident rollout log to the validation epoch's numbers.
+ * The metrics section of the C ABI of include/tbx_hip.h, exported by libtbx_hip.so like every other entry point (tbx_hip.h includes this
+ * header; its contract - device pointers to caller-owned buffers, nothing allocated or retained, kernels only enqueued on `stream`,
+ * TBX_* return codes - holds here too). Source: csrc/metrics.hip. It is the reduction of a device-resident rollout log to the
+ * validation epoch's numbers.
  */
 #ifndef TBX_HIP_METRICS_H
 #define TBX_HIP_METRICS_H

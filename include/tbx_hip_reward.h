@@ -1,10 +1,9 @@
 /*
- * libtbx_hip_reward.so - a library of its own beside libtbx_hip.so, under the contract of include/tbx_hip.h (which includes this header:
- * device pointers to caller-owned buffers, nothing allocated or retained, kernels only enqueued on `stream`, TBX_* return codes).
- * libtbx_hip.so's export list stays exactly ABI 7 + tbx_rollout_metrics; a host that wants the entry points below links / dlopens this
- * library as well (built by the same Makefile from csrc/collision.hip and csrc/train_chain.hip). They are
- * the reward term that couples the agents of a scene (differentiable_reward.w_collision > 0) and the training chain's reverse
- * walk with an adjoint of the predicted pose as a further input.
+ * The reward section of the C ABI of include/tbx_hip.h, exported by libtbx_hip.so like every other entry point (tbx_hip.h includes this
+ * header; its contract - device pointers to caller-owned buffers, nothing allocated or retained, kernels only enqueued on `stream`,
+ * TBX_* return codes - holds here too). Sources: csrc/collision.hip and csrc/train_chain.hip. The entry points are the reward term that
+ * couples the agents of a scene (differentiable_reward.w_collision > 0) and the training chain's reverse walk with an adjoint of the
+ * predicted pose as a further input.
  */
 #ifndef TBX_HIP_REWARD_H
 #define TBX_HIP_REWARD_H

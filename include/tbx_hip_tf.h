@@ -1,10 +1,9 @@
 /*
- * libtbx_hip_tf.so - a fourth library beside libtbx_hip.so, libtbx_hip_reward.so and libtbx_hip_loss.so, under the contract of
- * include/tbx_hip.h (which includes this header: device pointers to caller-owned buffers, nothing allocated or retained, kernels only
- * enqueued on `stream`, TBX_* return codes before any launch). libtbx_hip.so's export list stays exactly ABI 7 + tbx_rollout_metrics; a
- * host that wants the entry point below links / dlopens this library as well (built by the same Makefile from csrc/tf_threshold.hip).
- * It is the error-threshold form of teacher forcing (utils/teacher_forcing.py:128-151: threshold_xy, threshold_yaw, threshold_spd): an
- * agent whose simulated state has drifted from the logged one by more than a threshold is put back on the ground truth at the next step.
+ * The teacher-forcing section of the C ABI of include/tbx_hip.h, exported by libtbx_hip.so like every other entry point (tbx_hip.h
+ * includes this header; its contract - device pointers to caller-owned buffers, nothing allocated or retained, kernels only enqueued on
+ * `stream`, TBX_* return codes before any launch - holds here too). Source: csrc/tf_threshold.hip. It is the error-threshold form of
+ * teacher forcing (utils/teacher_forcing.py:128-151: threshold_xy, threshold_yaw, threshold_spd): an agent whose simulated state has
+ * drifted from the logged one by more than a threshold is put back on the ground truth at the next step.
  */
 #ifndef TBX_HIP_TF_H
 #define TBX_HIP_TF_H

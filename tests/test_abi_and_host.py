@@ -1,5 +1,5 @@
-"""CPU-only checks of the drop-in boundary: the C-ABI library loads and exports every symbol include/tbx_hip.h
-declares, argument validation returns error codes (no compute without a GPU), state-dict layout equals the reference's,
+"""CPU-only checks of the drop-in boundary: the C-ABI library loads and exports exactly the symbols include/tbx_hip.h and the
+topical headers it includes declare, argument validation returns error codes (no compute without a GPU), state-dict layout equals the reference's,
 host-side schedules (teacher forcing masks, scene-centric re-keying) equal the oracle's."""
 import ctypes as C
 from importlib import import_module
@@ -19,15 +19,36 @@ def hip(tb):
 
 
 def test_library_exports_every_declared_symbol(hip):
+    """One library, one symbol list: the tbx_* functions libtbx_hip.so exports are exactly the entry points include/tbx_hip.h and the four
+    topical headers it includes declare - 72 in its own text (ABI 7 as it was laid down) + 1 / 3 / 1 / 1 added since -, each bound with
+    argtypes, and the package names no other library."""
+    import re
+    import subprocess
+
     lib = hip.load()
     syms = hip.declared_symbols()
     assert set(syms) >= {"tbx_version", "tbx_error_string", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd",
-                         "tbx_rowchain", "tbx_rowchain_ex", "tbx_knarpe_attn_bwd", "tbx_agent_prep", "tbx_tl_prep", "tbx_map_prep", "tbx_sim_step"}
+                         "tbx_rowchain", "tbx_rowchain_ex", "tbx_knarpe_attn_bwd", "tbx_agent_prep", "tbx_tl_prep", "tbx_map_prep", "tbx_sim_step",
+                         "tbx_rollout_metrics", "tbx_collision_reward_fwd", "tbx_collision_reward_bwd", "tbx_train_chain_bwd_pose",
+                         "tbx_loss_shape", "tbx_tf_threshold"}
+    nm = subprocess.run(["nm", "-D", "--defined-only", str(hip.LIB_PATH)], check=True, capture_output=True, text=True).stdout
+    exported = [l.split()[2] for l in nm.splitlines() if len(l.split()) == 3 and l.split()[1] == "T" and l.split()[2].startswith("tbx_")]
+    assert sorted(exported) == sorted(syms) and len(syms) == 78
+    # ... counted header by header, each from its own text
+    main = hip.HEADER_PATH.read_text()
+    decl = r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\("
+    count = lambda txt: len(set(re.findall(decl, txt, flags=re.M)))
+    assert count(main) == 72
+    for name, n in (("tbx_hip_metrics.h", 1), ("tbx_hip_reward.h", 3), ("tbx_hip_loss.h", 1), ("tbx_hip_tf.h", 1)):
+        assert f'#include "{name}"' in main and count((hip.HEADER_PATH.parent / name).read_text()) == n, name
     for s in syms:
         assert hasattr(lib, s), s
-    assert lib.tbx_version() == 7
-    assert len(syms) == 72
+        assert getattr(lib, s).argtypes is not None or s in ("tbx_error_string", "tbx_version"), s  # (those two: called with what ctypes infers)
+    assert lib.tbx_version() == 7  # (an added entry point changes no existing one: no bump)
     assert lib.tbx_error_string(-2).decode().startswith("shape")
+    # no second library: the package's Python names libtbx_hip.so and, for profiling, libtbx_hip_clk.so
+    for py in sorted(hip.LIB_PATH.parent.parent.glob("*.py")):
+        assert set(re.findall(r"libtbx_hip_\w+\.so", py.read_text())) <= {"libtbx_hip_clk.so"}, py.name
 
 
 def test_argument_validation_returns_codes_without_a_gpu(hip):
@@ -144,7 +165,7 @@ def test_ctypes_mirrors_have_the_layout_gcc_gives_the_header(hip, tmp_path):
     pairs = [("tbx_stage_t", hip.Stage), ("tbx_attn_seg_t", hip.AttnSeg), ("tbx_attn_t", hip.Attn), ("tbx_dec_mid_t", hip.DecMid), ("tbx_dec_layer_t", hip.DecLayer), ("tbx_heads_tail_t", hip.HeadsTail), ("tbx_knn_job_t", hip.KnnJob), ("tbx_pose_embed_job_t", hip.PoseEmbedJob), ("tbx_sim_state_t", hip.SimState),
              ("tbx_train_chain_t", hip.TrainChainArgs), ("tbx_rule_ctx_t", hip.RuleCtx), ("tbx_layer_tile_t", hip.LayerTile),
              ("tbx_heads_tile_t", hip.HeadsTile), ("tbx_window_tile_t", hip.WindowTile), ("tbx_agent_prep_args_t", hip.AgentPrepArgs), ("tbx_tl_rows_t", hip.TlRows), ("tbx_front_t", hip.Front), ("tbx_tl_tail_t", hip.TlTail), ("tbx_pack_job_t", hip.PackJob),
-             ("tbx_drop_t", hip.Drop), ("tbx_linear_t", hip.Linear)]
+             ("tbx_drop_t", hip.Drop), ("tbx_linear_t", hip.Linear), ("tbx_loss_shape_t", hip.LossShape), ("tbx_tf_threshold_t", hip.TfThreshold)]
     src = tmp_path / "sz.c"
     # ... and offsetof of every field (same names on both sides): runs of same-sized pointers keep sizeof when two fields swap
     fields = [(c, t, f[0]) for c, t in pairs for f in t._fields_]
@@ -152,7 +173,7 @@ def test_ctypes_mirrors_have_the_layout_gcc_gives_the_header(hip, tmp_path):
                    "".join(f'printf("%zu\\n", sizeof({c}));' for c, _ in pairs) +
                    "".join(f'printf("%zu\\n", offsetof({c}, {f}));' for c, _, f in fields) + "return 0;}\n")
     exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", str(root / "include"), str(src), "-o", str(exe)], check=True)
+    subprocess.run(["gcc", "-Wall", "-Werror", "-I", str(root / "include"), str(src), "-o", str(exe)], check=True)
     out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     assert out[:len(pairs)] == [C.sizeof(t) for _, t in pairs]
     for (c, t, f), off in zip(fields, out[len(pairs):]):

@@ -188,7 +188,7 @@ def test_edge_semantics(hip, mode):
 def test_argument_checks_return_codes_without_a_launch(hip):
     """NULL pointers, sizes and strides that cannot be right, and more agents than the cap: TBX_ERR_ARG / TBX_ERR_UNSUPPORTED before any
     launch (the stand-in pointers below are never read)."""
-    lib = hip.load_reward()
+    lib = hip.load()
     P = 0x10000
     cap = hip.COLLISION_MAX_AG
 

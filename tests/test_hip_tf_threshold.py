@@ -221,13 +221,14 @@ def test_sampled_rollouts_of_a_scene_decide_independently(tb):
 
 
 def test_thresholds_off_launch_nothing_and_change_nothing(tb, hip, monkeypatch):
-    """Thresholds at -1: the wrapper is never called and the library never asked for - the rollout runs with load_tf() and the wrapper
-    made to raise, as in a build without the new library -, the eager one-queue step is its five launches, and the log equals the one of
-    an engine built before the library may be used again. With a threshold on the same step is those five launches + one."""
+    """Thresholds at -1: nothing of the threshold path is called - the rollout runs with hip.tf_threshold_launch, hip.tf_threshold_args and
+    hip.tf_threshold all made to raise, so nothing builds the arguments either -, the eager one-queue step is its five launches, and the
+    log equals the one of an engine built before the three may be used again. With a threshold on the same step is those five launches +
+    one."""
     E = import_module("trafficbots_amd.engine")
-    abi = import_module("trafficbots_amd.abi")
     counts = {"pair": 0, "tf": 0}
-    real_front, real_layer, real_tf, real_load = hip.launch_front_pair, hip.launch_dec_layer_pair, hip.tf_threshold_launch, abi.load_tf
+    real_front, real_layer, real_tf = hip.launch_front_pair, hip.launch_dec_layer_pair, hip.tf_threshold_launch
+    real_args, real_whole = hip.tf_threshold_args, hip.tf_threshold
     monkeypatch.setattr(hip, "launch_front_pair", lambda *a: (counts.__setitem__("pair", counts["pair"] + 1), real_front(*a))[1])
     monkeypatch.setattr(hip, "launch_dec_layer_pair", lambda *a: (counts.__setitem__("pair", counts["pair"] + 1), real_layer(*a))[1])
     T = 20
@@ -242,11 +243,12 @@ def test_thresholds_off_launch_nothing_and_change_nothing(tb, hip, monkeypatch):
                                             use_graph=g_)
         if thr is None:
             def refuse(*a, **k):
-                raise AssertionError("the threshold library was asked for with every threshold off")
-            monkeypatch.setattr(hip, "tf_threshold_launch", refuse), monkeypatch.setattr(hip, "load_tf", refuse), monkeypatch.setattr(abi, "load_tf", refuse)
+                raise AssertionError("the threshold path was entered with every threshold off")
+            for name in ("tf_threshold_launch", "tf_threshold_args", "tf_threshold"):
+                monkeypatch.setattr(hip, name, refuse)
         else:
             monkeypatch.setattr(hip, "tf_threshold_launch", lambda a: (counts.__setitem__("tf", counts["tf"] + 1), real_tf(a))[1])
-            monkeypatch.setattr(hip, "load_tf", real_load), monkeypatch.setattr(abi, "load_tf", real_load)
+            monkeypatch.setattr(hip, "tf_threshold_args", real_args), monkeypatch.setattr(hip, "tf_threshold", real_whole)
         counts.update(pair=0, tf=0)
         eager = run(False)
         assert wm._engine.one_queue and (wm._engine._tf_args is None) == (thr is None)

@@ -1,6 +1,6 @@
 """CPU checks of the training objective's loss shaping (temporal_discount, p_loss_for_irrelevant, w_relevant_agent): the float64
-restatement tests/loss_shape_ref.py against the reference's own numbers (tests/golden/loss_shape.npz), the C ABI of libtbx_hip_loss.so
-(header, export lists of all three libraries, argtypes, the ctypes mirror against gcc's layout, every refusal before a launch) and the
+restatement tests/loss_shape_ref.py against the reference's own numbers (tests/golden/loss_shape.npz), the C ABI of tbx_loss_shape
+(header, argtypes, every refusal before a launch; the export list and the ctypes mirror's layout: tests/test_abi_and_host.py) and the
 constructors that used to refuse the switches."""
 import ctypes as C
 import inspect
@@ -81,36 +81,23 @@ def test_restatement_reproduces_the_reference(fixture, name):
 
 
 def test_header_library_exports_and_argtypes_agree(hip):
-    lib = hip.load_loss()
-    assert hip.loss_symbols() == ["tbx_loss_shape"]
+    lib = hip.load()
+    assert "tbx_loss_shape" in hip.declared_symbols()
     assert lib.tbx_loss_shape.argtypes == [C.POINTER(hip.LossShape), C.c_void_p] and lib.tbx_loss_shape.restype is C.c_int
     assert '#include "tbx_hip_loss.h"' in hip.HEADER_PATH.read_text()
-
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", str(path)], check=True, capture_output=True, text=True).stdout
-        return sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("tbx_"))
-
-    assert exported(hip.LOSS_LIB_PATH) == hip.loss_symbols()
-    # the two libraries that were there export what they did: ABI 7's 72 declarations + tbx_rollout_metrics, and the reward library's three
-    main = exported(hip.LIB_PATH)
-    assert main == sorted(hip.declared_symbols() + hip.extension_symbols()) and len(main) == 73 and "tbx_rollout_metrics" in main
-    assert exported(hip.REWARD_LIB_PATH) == hip.reward_symbols() == ["tbx_collision_reward_bwd", "tbx_collision_reward_fwd", "tbx_train_chain_bwd_pose"]
-    assert hip.load().tbx_version() == 7
+    assert lib.tbx_version() == 7
 
 
-def test_ctypes_mirror_has_the_layout_gcc_gives_the_header(hip, tmp_path):
+def test_the_header_alone_compiles_and_defines_the_workspace_size(hip, tmp_path):
+    """tbx_hip_loss.h included first (it includes tbx_hip.h for the codes) compiles as C with -Wall -Werror, and TBX_LOSS_PARTIALS is the
+    ctypes module's LOSS_PARTIALS. (sizeof / offsetof of tbx_loss_shape_t against hip.LossShape: tests/test_abi_and_host.py.)"""
     root = Path(__file__).resolve().parent.parent
-    fields = [f[0] for f in hip.LossShape._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include "tbx_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void){printf("%zu\\n", sizeof(tbx_loss_shape_t));'
-                   + "".join(f'printf("%zu\\n", offsetof(tbx_loss_shape_t, {f}));' for f in fields) + 'printf("%d\\n", TBX_LOSS_PARTIALS);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", str(root / "include"), str(src), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == C.sizeof(hip.LossShape)
-    for f, off in zip(fields, out[1:-1]):
-        assert getattr(hip.LossShape, f).offset == off, (f, getattr(hip.LossShape, f).offset, off)
-    assert out[-1] == hip.LOSS_PARTIALS
+    src = tmp_path / "alone.c"
+    src.write_text('#include "tbx_hip_loss.h"\n#include <stdio.h>\nint main(void){printf("%d\\n", TBX_LOSS_PARTIALS);'
+                   'return (int)sizeof(tbx_loss_shape_t) == 0;}\n')
+    exe = tmp_path / "alone"
+    subprocess.run(["gcc", "-Wall", "-Werror", "-I", str(root / "include"), str(src), "-o", str(exe)], check=True)
+    assert int(subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout) == hip.LOSS_PARTIALS
 
 
 def _stand_in(hip, **over):
@@ -126,7 +113,7 @@ def _stand_in(hip, **over):
 
 
 def test_every_refusal_returns_its_code_before_a_launch(hip):
-    lib = hip.load_loss()
+    lib = hip.load()
     ARG, UNSUPPORTED = -1, -2  # TBX_ERR_ARG, TBX_ERR_UNSUPPORTED
     assert lib.tbx_loss_shape(None, None) == ARG
     assert lib.tbx_loss_shape(C.byref(_stand_in(hip)), None) == 0  # rows == 0: nothing to do, nothing launched

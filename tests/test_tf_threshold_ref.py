@@ -1,7 +1,7 @@
 """CPU checks of error-threshold teacher forcing (TeacherForcing's threshold_xy / threshold_yaw / threshold_spd): the torch restatement
 tests/tf_threshold_ref.py and `TeacherForcing.get` on CPU tensors against the reference's own results (tests/golden/tf_threshold.npz), the
-C ABI of libtbx_hip_tf.so (header, export lists, argtypes, the ctypes mirror against gcc's layout, every refusal before a launch) and the
-constructor that used to refuse the thresholds."""
+C ABI of tbx_tf_threshold (header, argtypes, every refusal before a launch; the export list and the ctypes mirror's layout:
+tests/test_abi_and_host.py) and the constructor that used to refuse the thresholds."""
 import ctypes as C
 import subprocess
 import sys
@@ -110,37 +110,17 @@ def test_thresholds_off_leave_get_and_the_table_as_they_were(cases, TF):
 
 
 def test_header_library_exports_and_argtypes_agree(hip):
-    lib = hip.load_tf()
-    assert hip.tf_symbols() == ["tbx_tf_threshold"]
+    lib = hip.load()
+    assert "tbx_tf_threshold" in hip.declared_symbols()
     assert lib.tbx_tf_threshold.argtypes == [C.POINTER(hip.TfThreshold), C.c_void_p] and lib.tbx_tf_threshold.restype is C.c_int
     assert '#include "tbx_hip_tf.h"' in hip.HEADER_PATH.read_text()
-
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", str(path)], check=True, capture_output=True, text=True).stdout
-        return sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("tbx_"))
-
-    assert exported(hip.TF_LIB_PATH) == hip.tf_symbols()
-    # the three libraries that were there export what they did
-    main = exported(hip.LIB_PATH)
-    assert main == sorted(hip.declared_symbols() + hip.extension_symbols()) and len(main) == 73 and "tbx_tf_threshold" not in main
-    assert exported(hip.REWARD_LIB_PATH) == hip.reward_symbols() == ["tbx_collision_reward_bwd", "tbx_collision_reward_fwd", "tbx_train_chain_bwd_pose"]
-    assert exported(hip.LOSS_LIB_PATH) == hip.loss_symbols() == ["tbx_loss_shape"]
-    assert hip.load().tbx_version() == 7
+    assert lib.tbx_version() == 7
 
 
-def test_ctypes_mirror_has_the_layout_gcc_gives_the_header(hip, tmp_path):
+def test_the_header_alone_compiles(tmp_path):
+    """tbx_hip_tf.h included first (it includes tbx_hip.h for the codes) compiles as C with -Wall -Werror. (sizeof / offsetof of
+    tbx_tf_threshold_t against hip.TfThreshold: tests/test_abi_and_host.py.)"""
     root = Path(__file__).resolve().parent.parent
-    fields = [f[0] for f in hip.TfThreshold._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include "tbx_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void){printf("%zu\\n", sizeof(tbx_tf_threshold_t));'
-                   + "".join(f'printf("%zu\\n", offsetof(tbx_tf_threshold_t, {f}));' for f in fields) + 'return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-Wall", "-Werror", "-I", str(root / "include"), str(src), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == C.sizeof(hip.TfThreshold)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(hip.TfThreshold, f).offset == off, (f, getattr(hip.TfThreshold, f).offset, off)
-    # the header alone compiles too (it includes tbx_hip.h for the codes)
     alone = tmp_path / "alone.c"
     alone.write_text('#include "tbx_hip_tf.h"\nint main(void){return (int)sizeof(tbx_tf_threshold_t) == 0;}\n')
     subprocess.run(["gcc", "-Wall", "-Werror", "-I", str(root / "include"), str(alone), "-o", str(tmp_path / "alone")], check=True)
@@ -161,7 +141,7 @@ def _stand_in(hip, **over):
 
 
 def test_every_refusal_returns_its_code_before_a_launch(hip):
-    lib = hip.load_tf()
+    lib = hip.load()
     ARG, UNSUPPORTED = -1, -2  # TBX_ERR_ARG, TBX_ERR_UNSUPPORTED
     assert lib.tbx_tf_threshold(None, None) == ARG
     assert lib.tbx_tf_threshold(C.byref(_stand_in(hip)), None) == 0  # n_rows == 0: nothing to do, nothing launched

@@ -1,7 +1,8 @@
-"""The C-ABI mirror: constants and ctypes structures of include/tbx_hip.h, and `load()` - dlopen of the in-tree libtbx_hip.so with
-every declared symbol checked and every prototype set. Nothing here computes; the wrappers that launch kernels are in hip.py
-(which re-exports this module's names). tests/test_abi_and_host.py compiles the header with gcc and compares every structure's
-`sizeof` and every field's `offsetof` with the classes below."""
+"""The C-ABI mirror: constants and ctypes structures of include/tbx_hip.h and the topical headers it includes (tbx_hip_metrics.h, _reward.h,
+_loss.h, _tf.h), and `load()` - dlopen of the in-tree libtbx_hip.so, the one library, with every declared symbol checked and every
+prototype set. Nothing here computes; the wrappers that launch kernels are in hip.py (which re-exports this module's names).
+tests/test_abi_and_host.py compiles the header with gcc and compares every structure's `sizeof` and every field's `offsetof` with the
+classes below."""
 import ctypes as C
 import os
 import re
@@ -11,14 +12,7 @@ from typing import List
 _lib = None
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "csrc" / "libtbx_hip.so"
-REWARD_LIB_PATH = _PKG / "csrc" / "libtbx_hip_reward.so"  # the entry points of include/tbx_hip_reward.h: a library of their own
-LOSS_LIB_PATH = _PKG / "csrc" / "libtbx_hip_loss.so"  # the entry point of include/tbx_hip_loss.h: a third library
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
-REWARD_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_reward.h"
-LOSS_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_loss.h"
-TF_LIB_PATH = _PKG / "csrc" / "libtbx_hip_tf.so"  # the entry point of include/tbx_hip_tf.h: a fourth library
-TF_HEADER_PATH = HEADER_PATH.parent / "tbx_hip_tf.h"
-EXTENSION_HEADER_PATHS = (HEADER_PATH.parent / "tbx_hip_metrics.h",)  # included by tbx_hip.h: entry points added after ABI 7 was laid down
 
 # ---- constants mirrored from include/tbx_hip.h
 OP_LOAD, OP_LINEAR, OP_LAYERNORM, OP_ADD, OP_COPY, OP_ROWMASK, OP_GROUPMAX, OP_POOLMAX, OP_STORE, OP_CLAMP, OP_DROPOUT = range(1, 12)
@@ -229,140 +223,37 @@ COLLISION_MAX_AG, COLLISION_LANES = 512, 4  # TBX_COLLISION_* of include/tbx_hip
 METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
 LOSS_PARTIALS = 512  # TBX_LOSS_PARTIALS of include/tbx_hip_loss.h: tbx_loss_shape's float64 workspace
 
-_lib = None
-
-
 _DECL = r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\("
 
 
 def declared_symbols() -> List[str]:
-    """Entry points declared in include/tbx_hip.h (the C-ABI contract)."""
+    """Entry points declared in include/tbx_hip.h and in the topical tbx_*.h headers it includes (the C-ABI contract): everything
+    libtbx_hip.so exports."""
     txt = HEADER_PATH.read_text()
+    for name in re.findall(r'^#include "(tbx_\w+\.h)"', txt, flags=re.M):
+        txt += (HEADER_PATH.parent / name).read_text()
     return sorted(set(re.findall(_DECL, txt, flags=re.M)))
 
 
-def extension_symbols() -> List[str]:
-    """Entry points declared in the extension headers include/tbx_hip.h includes (tbx_rollout_metrics): with declared_symbols(),
-    everything the library exports."""
-    included = set(re.findall(r'^#include "(tbx_\w+\.h)"', HEADER_PATH.read_text(), flags=re.M))
-    missing = [p.name for p in EXTENSION_HEADER_PATHS if p.name not in included]
-    if missing:
-        raise ImportError(f"include/tbx_hip.h does not include {missing}")
-    return sorted({s for p in EXTENSION_HEADER_PATHS for s in re.findall(_DECL, p.read_text(), flags=re.M)})
-
-
-def reward_symbols() -> List[str]:
-    """Entry points declared in include/tbx_hip_reward.h: what libtbx_hip_reward.so exports."""
-    return sorted(set(re.findall(_DECL, REWARD_HEADER_PATH.read_text(), flags=re.M)))
-
-
-_reward_lib = None
-
-
-def load_reward():
-    """dlopen the in-tree libtbx_hip_reward.so (the collision term's kernel pair, the training chain's reverse walk with a pose adjoint) and
-    check it exports every symbol its header declares. No GPU needed. A missing library is an error: there is no fallback path."""
-    global _reward_lib
-    if _reward_lib is not None:
-        return _reward_lib
-    load()  # (the error strings / ABI version check of the main library)
-    if not REWARD_LIB_PATH.exists():
-        raise ImportError(f"{REWARD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`. There is no fallback path.")
-    lib = C.CDLL(str(REWARD_LIB_PATH))
-    for s in reward_symbols():
-        if not hasattr(lib, s):
-            raise ImportError(f"libtbx_hip_reward.so does not export {s}")
-    i32, i64, vp = C.c_int, C.c_int64, C.c_void_p
-    lib.tbx_collision_reward_fwd.argtypes = [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, vp, i32, vp, i64, i64, i64, vp, vp]
-    lib.tbx_collision_reward_bwd.argtypes = [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, vp, i32, vp, i64, i64, i64, vp, vp, vp]
-    lib.tbx_train_chain_bwd_pose.argtypes = [C.POINTER(TrainChainArgs), vp, i64, i64, vp, vp, vp, vp]
-    untyped = [s for s in reward_symbols() if getattr(lib, s).argtypes is None]
-    if untyped:
-        raise ImportError(f"abi.load_reward(): no argtypes for {untyped}")
-    for s in reward_symbols():
-        getattr(lib, s).restype = C.c_int
-    _reward_lib = lib
-    return lib
-
-
-def loss_symbols() -> List[str]:
-    """Entry points declared in include/tbx_hip_loss.h: what libtbx_hip_loss.so exports."""
-    return sorted(set(re.findall(_DECL, LOSS_HEADER_PATH.read_text(), flags=re.M)))
-
-
-_loss_lib = None
-
-
-def load_loss():
-    """dlopen the in-tree libtbx_hip_loss.so (tbx_loss_shape: the loss shaping of the training objective) and check it exports every symbol
-    its header declares. No GPU needed. A missing library is an error: there is no fallback path."""
-    global _loss_lib
-    if _loss_lib is not None:
-        return _loss_lib
-    load()  # (the error strings / ABI version check of the main library)
-    if not LOSS_LIB_PATH.exists():
-        raise ImportError(f"{LOSS_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`. There is no fallback path.")
-    lib = C.CDLL(str(LOSS_LIB_PATH))
-    for s in loss_symbols():
-        if not hasattr(lib, s):
-            raise ImportError(f"libtbx_hip_loss.so does not export {s}")
-    lib.tbx_loss_shape.argtypes = [C.POINTER(LossShape), C.c_void_p]
-    untyped = [s for s in loss_symbols() if getattr(lib, s).argtypes is None]
-    if untyped:
-        raise ImportError(f"abi.load_loss(): no argtypes for {untyped}")
-    for s in loss_symbols():
-        getattr(lib, s).restype = C.c_int
-    _loss_lib = lib
-    return lib
-
-
-def tf_symbols() -> List[str]:
-    """Entry points declared in include/tbx_hip_tf.h: what libtbx_hip_tf.so exports."""
-    return sorted(set(re.findall(_DECL, TF_HEADER_PATH.read_text(), flags=re.M)))
-
-
-_tf_lib = None
-
-
-def load_tf():
-    """dlopen the in-tree libtbx_hip_tf.so (tbx_tf_threshold: the error-threshold resets of teacher forcing) and check it exports every
-    symbol its header declares. No GPU needed. A missing library is an error: there is no fallback path."""
-    global _tf_lib
-    if _tf_lib is not None:
-        return _tf_lib
-    load()  # (the error strings / ABI version check of the main library)
-    if not TF_LIB_PATH.exists():
-        raise ImportError(f"{TF_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`. There is no fallback path.")
-    lib = C.CDLL(str(TF_LIB_PATH))
-    for s in tf_symbols():
-        if not hasattr(lib, s):
-            raise ImportError(f"libtbx_hip_tf.so does not export {s}")
-    lib.tbx_tf_threshold.argtypes = [C.POINTER(TfThreshold), C.c_void_p]
-    untyped = [s for s in tf_symbols() if getattr(lib, s).argtypes is None]
-    if untyped:
-        raise ImportError(f"abi.load_tf(): no argtypes for {untyped}")
-    for s in tf_symbols():
-        getattr(lib, s).restype = C.c_int
-    _tf_lib = lib
-    return lib
-
-
 def load():
-    """dlopen the in-tree library and check it exports every declared symbol. No GPU needed."""
+    """dlopen the in-tree libtbx_hip.so (or the build TBX_HIP_LIB names), check it exports every declared symbol and set every prototype.
+    No GPU needed. A missing library is an error: there is no fallback path."""
     global _lib
     if _lib is not None:
         return _lib
-    lib_path = Path(os.environ.get("TBX_HIP_LIB", LIB_PATH))  # profiling builds only (tools/stage_clock.py)
+    lib_path = Path(os.environ.get("TBX_HIP_LIB", LIB_PATH))  # profiling / host-sanitizer builds only (tools/stage_clock.py, tools/sanitize_host.sh)
     if not lib_path.exists():
         raise ImportError(
             f"{lib_path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no fallback path.")
     lib = C.CDLL(str(lib_path))
-    for s in declared_symbols() + extension_symbols():
+    symbols = declared_symbols()
+    for s in symbols:
         if not hasattr(lib, s):
             raise ImportError(f"libtbx_hip.so does not export {s}")
+    for s in symbols:  # (tbx_version included; the *_size functions below return int64_t)
+        getattr(lib, s).restype = C.c_int
     lib.tbx_error_string.restype = C.c_char_p
-    lib.tbx_version.restype = C.c_int
     i32, i64, f32, vp = C.c_int, C.c_int64, C.c_float, C.c_void_p
     lib.tbx_knn_embed.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.tbx_pose_embed.argtypes = [vp, i64, vp, vp, i32, vp, i32, i32, vp]
@@ -439,14 +330,15 @@ def load():
     lib.tbx_attn_fold_bwd.argtypes = [vp] * 19
     lib.tbx_rule_navi_check.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.tbx_rollout_metrics.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    for name in ("tbx_layer_tile", "tbx_heads_tile", "tbx_window_tile", "tbx_front", "tbx_tall_linear", "tbx_pack_weight_mfma32", "tbx_pack_weight_mfma32_multi", "tbx_pack_weight", "tbx_pack_weight_split", "tbx_pack_weight_gemv", "tbx_rowchain_live", "tbx_knarpe_dec_mid", "tbx_knarpe_dec_layer", "tbx_knn_embed_multi", "tbx_knn_embed", "tbx_pose_embed", "tbx_knarpe_attn_fwd", "tbx_knarpe_attn_bwd", "tbx_keyed_dropout", "tbx_linear_wgrad_splits", "tbx_linear_wgrad", "tbx_linear_wgrad_bf16", "tbx_tall_linear_bf16", "tbx_tl_tail_tile", "tbx_tl_tail_tile_bf16", "tbx_layernorm_fwd", "tbx_layernorm_bwd_partials", "tbx_layernorm_bwd", "tbx_layernorm_bwd_add", "tbx_residual_drop_fwd", "tbx_residual_drop_bwd", "tbx_relu_drop_fwd", "tbx_relu_drop_bwd", "tbx_pair_bias_relu", "tbx_pointnet_tail_fwd", "tbx_pointnet_tail_bwd", "tbx_masked_maxpool_fwd", "tbx_masked_maxpool_bwd", "tbx_train_chain_fwd", "tbx_train_chain_fwd_windows", "tbx_train_chain_bwd", "tbx_knn_inverse", "tbx_rowchain", "tbx_rowchain_ex", "tbx_agent_prep", "tbx_tl_prep",
-                 "tbx_map_prep", "tbx_sim_step", "tbx_rule_tables", "tbx_rule_grid", "tbx_rule_grid_cells", "tbx_rule_check", "tbx_rule_accumulate", "tbx_filter_futures", "tbx_rule_navi_check", "tbx_attn_fold_fwd", "tbx_attn_fold_bwd", "tbx_front_pair", "tbx_knarpe_dec_layer_pair",
-                 "tbx_womd_modes", "tbx_pose_to_global", "tbx_rel_pose_dense", "tbx_diffbar_reward", "tbx_knarpe_attn_fwd_mfma", "tbx_rollout_metrics"):
-        getattr(lib, name).restype = C.c_int
+    lib.tbx_collision_reward_fwd.argtypes = [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, vp, i32, vp, i64, i64, i64, vp, vp]
+    lib.tbx_collision_reward_bwd.argtypes = [vp, vp, i64, i32, i32, i32, i64, i64, i64, i64, i64, i64, vp, i32, vp, i64, i64, i64, vp, vp, vp]
+    lib.tbx_train_chain_bwd_pose.argtypes = [C.POINTER(TrainChainArgs), vp, i64, i64, vp, vp, vp, vp]
+    lib.tbx_loss_shape.argtypes = [C.POINTER(LossShape), vp]
+    lib.tbx_tf_threshold.argtypes = [C.POINTER(TfThreshold), vp]
     if lib.tbx_version() != 7:
         raise ImportError("libtbx_hip.so ABI version mismatch")
     # (an entry point without argtypes would get 64-bit handles - stream pointers under graph capture - as C ints)
-    untyped = [s for s in declared_symbols() + extension_symbols() if getattr(lib, s).argtypes is None and s not in ("tbx_error_string", "tbx_version")]
+    untyped = [s for s in symbols if getattr(lib, s).argtypes is None and s not in ("tbx_error_string", "tbx_version")]
     if untyped:
         raise ImportError(f"abi.load(): no argtypes for {untyped}")
     _lib = lib

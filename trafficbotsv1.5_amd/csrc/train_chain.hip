@@ -21,7 +21,6 @@ __device__ __forceinline__ float sl1(float d) {  // F.smooth_l1_loss, beta = 1
 }
 __device__ __forceinline__ float sl1_grad(float d) { return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f); }
 
-#ifndef TBX_REWARD_EXT  // (the reward extension's build of this file holds the reverse walk only, see the end of the file)
 // The policy inputs of the NEXT step in the layout the policy reads them in (tbx_train_chain_fwd_windows): the W-step windows [n, A, W
 // (, 3)], oldest first, and the current validity / navigation flags - written by the thread that owns the agent, behind its step (the
 // stepping pass spent six strided-copy launches per closed-loop step on these).
@@ -162,8 +161,6 @@ __global__ __launch_bounds__(64) void train_chain_fwd_kernel(const tbx_train_cha
   }
 }
 
-#endif  // !TBX_REWARD_EXT
-
 // d(mean) from d(reward), all steps, in reverse. Reads what the forward over [0, T) left behind: the records of the state
 // before every step (slot window - 1 + t holds the state before step t + 1), the override flags and the predictions.
 __global__ __launch_bounds__(64) void train_chain_bwd_kernel(const tbx_train_chain_t c, const float* __restrict__ mean, int64_t sn,
@@ -243,7 +240,6 @@ static int launch_bwd(const tbx_train_chain_t* c, const float* mean, int64_t mea
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 
-#ifndef TBX_REWARD_EXT
 extern "C" int tbx_train_chain_fwd(const tbx_train_chain_t* c, const float* mean, int64_t mean_stride_n, int64_t mean_stride_t, int t0,
                                    int t1, void* stream) {
   const int rc = check(c);
@@ -270,11 +266,9 @@ extern "C" int tbx_train_chain_bwd(const tbx_train_chain_t* c, const float* mean
                                    const float* d_reward, float* d_mean, void* stream) {
   return launch_bwd(c, mean, mean_stride_n, mean_stride_t, d_reward, nullptr, d_mean, stream);
 }
-#else
-// libtbx_hip_reward.so (include/tbx_hip_reward.h): this file compiled once more with TBX_REWARD_EXT - the same reverse-walk kernel, launched
-// with the adjoint of the predicted pose. libtbx_hip.so's export list stays the one of ABI 7 + tbx_rollout_metrics.
+
+// (include/tbx_hip_reward.h) the same reverse walk with the adjoint of the predicted pose
 extern "C" int tbx_train_chain_bwd_pose(const tbx_train_chain_t* c, const float* mean, int64_t mean_stride_n, int64_t mean_stride_t,
                                         const float* d_reward, const float* d_pred_pose, float* d_mean, void* stream) {
   return launch_bwd(c, mean, mean_stride_n, mean_stride_t, d_reward, d_pred_pose, d_mean, stream);
 }
-#endif

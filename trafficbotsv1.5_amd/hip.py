@@ -1,4 +1,4 @@
-"""ctypes binding of libtbx_hip.so (include/tbx_hip.h) + the `Chain` builder for tbx_rowchain programs.
+"""ctypes binding of libtbx_hip.so (include/tbx_hip.h and the topical tbx_hip_*.h headers it includes) + the `Chain` builder for tbx_rowchain programs.
 
 The HIP library IS the product path: there is no CPU or PyTorch fallback. `load()` raises if the shared object is
 missing, and every wrapper raises on a non-zero tbx return code or on tensors that are not on a HIP device.
@@ -472,7 +472,7 @@ def _flag8(t: Optional[torch.Tensor], shape, what: str, who: str = "loss_shape")
 def loss_shape(pred_valid, tf, step_training_start: int, loss_for_teacher_forcing: bool, reward=None, reward_valid=None, relevant=None,
                pick=None, mask_irrelevant: bool = False, w_relevant: float = 0.0, discount: float = -1.0, want_w: bool = False, acc=None,
                partials=None):
-    """tbx_loss_shape (libtbx_hip_loss.so) on [rows, A, T] VIEWS of any strides - the training chain's permuted [n, T, A] log, a buffer's
+    """tbx_loss_shape (include/tbx_hip_loss.h) on [rows, A, T] VIEWS of any strides - the training chain's permuted [n, T, A] log, a buffer's
     [rows, A, T], a time slice of the engine's log: read in place. pred_valid / tf / reward_valid u8 or bool, reward f32; relevant / pick
     [rows, A] u8 or bool, contiguous. -> (any_valid u8 [rows, A], w_agent f32 [rows, A], w f32 [rows, A, T] | None, acc f64 [2] | None):
     acc[0] = the shaped reward sum, acc[1] = #rv, ADDED to `acc` if one is passed (else to zeros); without reward: masks only."""
@@ -504,7 +504,7 @@ def loss_shape(pred_valid, tf, step_training_start: int, loss_for_teacher_forcin
     a.n_ag, a.n_step, a.step_training_start = A, T, int(step_training_start)
     a.loss_for_teacher_forcing, a.mask_irrelevant = int(bool(loss_for_teacher_forcing)), int(bool(mask_irrelevant))
     a.w_relevant, a.discount = float(w_relevant), float(discount)
-    _check(load_loss().tbx_loss_shape(C.byref(a), stream_ptr()), "tbx_loss_shape")
+    _check(load().tbx_loss_shape(C.byref(a), stream_ptr()), "tbx_loss_shape")
     return any_valid, w_agent, w, acc
 
 
@@ -534,8 +534,8 @@ def tf_threshold_args(thresholds, step, valid, pose, motion, gt_valid, gt_pose, 
 
 
 def tf_threshold_launch(a: "TfThreshold") -> None:
-    """tbx_tf_threshold (libtbx_hip_tf.so) on the current stream: one step's error-threshold resets ORed into column s of a.tf_mask."""
-    _check(load_tf().tbx_tf_threshold(C.byref(a), stream_ptr()), "tbx_tf_threshold")
+    """tbx_tf_threshold (include/tbx_hip_tf.h) on the current stream: one step's error-threshold resets ORed into column s of a.tf_mask."""
+    _check(load().tbx_tf_threshold(C.byref(a), stream_ptr()), "tbx_tf_threshold")
 
 
 def tf_threshold(thresholds, step, valid, pose, motion, gt_valid, gt_pose, gt_motion, tf_mask, out_reset=None) -> None:

@@ -1,6 +1,7 @@
 """ctypes wrappers of the TRAINING entry points of libtbx_hip.so (include/tbx_hip.h): keyed dropout and the one-pass glue ops, the tall
 LINEAR / weight-gradient kernels of the time-batched pass, LayerNorm / PointNet-tail / masked-max-pool forward + backward, the attention
-backward (atomics and inverse-list forms) and the per-step state machine (tbx_train_chain_*). Re-exported by hip.py."""
+backward (atomics and inverse-list forms), the per-step state machine (tbx_train_chain_*) and the collision term of the reward
+(include/tbx_hip_reward.h). Re-exported by hip.py."""
 import ctypes as C
 import os
 from typing import List, Optional, Sequence
@@ -8,7 +9,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
-from .abi import load, load_reward  # noqa: F401
+from .abi import load  # noqa: F401
 from .hip_base import Seg, _attn_args, _check, _cptr, _derived, _name, _ptr, drop_mix, drop_rate, drop_stream_key, drop_struct, packed_weight, stream_ptr
 
 
@@ -327,7 +328,7 @@ def train_chain_bwd(args: TrainChainArgs, mean: torch.Tensor, stride_n: int, str
 def train_chain_bwd_pose(args: TrainChainArgs, mean: torch.Tensor, stride_n: int, stride_t: int, d_reward: torch.Tensor,
                          d_pred_pose: Optional[torch.Tensor], d_mean: torch.Tensor):
     """tbx_train_chain_bwd_pose: the reverse walk with d_pred_pose [n,T,A,3] (None: tbx_train_chain_bwd) added to the predictions' adjoint."""
-    _check(load_reward().tbx_train_chain_bwd_pose(C.byref(args), _ptr(mean, torch.float32), stride_n, stride_t, _ptr(d_reward, torch.float32),
+    _check(load().tbx_train_chain_bwd_pose(C.byref(args), _ptr(mean, torch.float32), stride_n, stride_t, _ptr(d_reward, torch.float32),
                                            _cptr(d_pred_pose, torch.float32), _ptr(d_mean, torch.float32), stream_ptr()), "tbx_train_chain_bwd_pose")
 
 
@@ -349,7 +350,7 @@ def collision_reward_fwd(pose: torch.Tensor, valid: torch.Tensor, ag_size: torch
     c = torch.empty(rows, T, A, dtype=torch.float32, device=pose.device) if out is None else out
     assert tuple(c.shape) == (rows, T, A) and c.dtype == torch.float32
     arg = torch.empty(rows, T, A, dtype=torch.int32, device=pose.device) if (want_arg and reduce_with_max) else None
-    _check(load_reward().tbx_collision_reward_fwd(*_collision_log_args(pose, valid, ag_size, n_k), int(bool(reduce_with_max)), _ptr(c), c.stride(0),
+    _check(load().tbx_collision_reward_fwd(*_collision_log_args(pose, valid, ag_size, n_k), int(bool(reduce_with_max)), _ptr(c), c.stride(0),
                                            c.stride(2), c.stride(1), _ptr(arg), stream_ptr()), "tbx_collision_reward_fwd")
     return c, arg
 
@@ -361,6 +362,6 @@ def collision_reward_bwd(pose: torch.Tensor, valid: torch.Tensor, ag_size: torch
     assert tuple(g.shape) == (rows, T, A) and g.dtype == torch.float32
     assert arg is None or (arg.is_contiguous() and tuple(arg.shape) == (rows, T, A))
     d_pose = torch.empty(rows, T, A, 3, dtype=torch.float32, device=pose.device)
-    _check(load_reward().tbx_collision_reward_bwd(*_collision_log_args(pose, valid, ag_size, n_k), int(bool(reduce_with_max)), _ptr(g), g.stride(0),
+    _check(load().tbx_collision_reward_bwd(*_collision_log_args(pose, valid, ag_size, n_k), int(bool(reduce_with_max)), _ptr(g), g.stride(0),
                                            g.stride(2), g.stride(1), _ptr(arg, torch.int32), _ptr(d_pose), stream_ptr()), "tbx_collision_reward_bwd")
     return d_pose
