@@ -10,8 +10,10 @@ from pathlib import Path
 from typing import List
 
 _lib = None
+_grad_lib = None
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "csrc" / "libtbx_hip.so"
+GRAD_LIB_PATH = _PKG / "csrc" / "libtbx_grad.so"  # tbx_grad_norms alone (include/tbx_hip_grad.h): libtbx_hip.so's export list is ABI 7's, closed
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
 
 # ---- constants mirrored from include/tbx_hip.h
@@ -218,10 +220,18 @@ class TfThreshold(C.Structure):
                 + [(n, C.c_float) for n in ("threshold_xy", "threshold_yaw", "threshold_spd", "pad2_")])
 
 
+class GradNorms(C.Structure):
+    """tbx_grad_norms_t (include/tbx_hip_grad.h: the one entry point of libtbx_grad.so, `load_grad()`). Filled by hip.grad_norms_args."""
+    _fields_ = ([(n, C.c_void_p) for n in ("g", "seg_off", "seg_len", "chunk_seg", "chunk_off", "chunk_len", "partial", "partial_nf", "norms",
+                                           "total", "nonfinite", "coef")] + [("n", C.c_int64)]
+                + [(n, C.c_int32) for n in ("n_seg", "n_chunk", "chunk_max", "norm_type")] + [("max_norm", C.c_double)])
+
+
 RULE_COLLIDED, RULE_COLLIDED_WOSAC, RULE_RUN_ROAD_EDGE, RULE_RUN_RED_LIGHT, RULE_PASSIVE = 1, 2, 4, 8, 16
 COLLISION_MAX_AG, COLLISION_LANES = 512, 4  # TBX_COLLISION_* of include/tbx_hip_reward.h: the collision kernels' agent cap / lanes per agent
 METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
 LOSS_PARTIALS = 512  # TBX_LOSS_PARTIALS of include/tbx_hip_loss.h: tbx_loss_shape's float64 workspace
+GRAD_CHUNK, GRAD_NORM_2, GRAD_NORM_INF = 8192, 2, 0  # TBX_GRAD_* of include/tbx_hip_grad.h: tbx_grad_norms' chunk size and norm types
 
 _DECL = r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\("
 
@@ -342,4 +352,22 @@ def load():
     if untyped:
         raise ImportError(f"abi.load(): no argtypes for {untyped}")
     _lib = lib
+    return lib
+
+
+def load_grad():
+    """dlopen the in-tree libtbx_grad.so (built by the same Makefile) and set the prototype of its one entry point, tbx_grad_norms
+    (include/tbx_hip_grad.h). No GPU needed. A missing library is an error: there is no fallback path."""
+    global _grad_lib
+    if _grad_lib is not None:
+        return _grad_lib
+    if not GRAD_LIB_PATH.exists():
+        raise ImportError(f"{GRAD_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                          "(hipcc --offload-arch=gfx950). There is no fallback path.")
+    lib = C.CDLL(str(GRAD_LIB_PATH))
+    if not hasattr(lib, "tbx_grad_norms"):
+        raise ImportError("libtbx_grad.so does not export tbx_grad_norms")
+    lib.tbx_grad_norms.restype = C.c_int
+    lib.tbx_grad_norms.argtypes = [C.POINTER(GradNorms), C.c_void_p]
+    _grad_lib = lib
     return lib

@@ -13,7 +13,7 @@ import torch
 
 from . import abi, hip_base
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
-from .abi import HEADER_PATH, LIB_PATH, load  # noqa: F401
+from .abi import GRAD_LIB_PATH, HEADER_PATH, LIB_PATH, load, load_grad  # noqa: F401
 from .hip_base import *  # noqa: F401,F403  (Seg, stream_ptr, packed_weight / stacked_linear / padded_weight)
 from .hip_base import _attn_args, _check, _cptr, _fill_drop, _ptr  # noqa: F401
 from .hip_chain import *  # noqa: F401,F403  (Chain, group_tile_rows)
@@ -541,3 +541,32 @@ def tf_threshold_launch(a: "TfThreshold") -> None:
 def tf_threshold(thresholds, step, valid, pose, motion, gt_valid, gt_pose, gt_motion, tf_mask, out_reset=None) -> None:
     """tf_threshold_args + tf_threshold_launch: utils/teacher_forcing.py:131-145 for one step, in place on tf_mask [rows, A, Tg]."""
     tf_threshold_launch(tf_threshold_args(thresholds, step, valid, pose, motion, gt_valid, gt_pose, gt_motion, tf_mask, out_reset))
+
+
+def grad_norms_args(g, seg_off, seg_len, chunk_seg, chunk_off, chunk_len, chunk_max: int, partial, partial_nf, out, norm_type: int,
+                    max_norm: Optional[float]) -> "GradNorms":
+    """tbx_grad_norms_t over the caller's tensors (include/tbx_hip_grad.h): g the flat f32 buffer; the segment / chunk tables and the two
+    workspaces as FlatGrads.norm_plan() lays them out; `out` f32 [n_seg + 3] = norms | total | coef | nonfinite (the last word read as
+    i32). norm_type GRAD_NORM_2 / GRAD_NORM_INF; max_norm None or <= 0: no clipping. The struct holds pointers only: the caller keeps the
+    tensors alive."""
+    n_seg, n_chunk = seg_off.numel(), chunk_seg.numel()
+    if g.dim() != 1 or seg_len.numel() != n_seg or chunk_off.numel() != n_chunk or chunk_len.numel() != n_chunk:
+        raise TypeError("grad_norms: g must be flat, seg_off / seg_len and chunk_seg / chunk_off / chunk_len of one length each")
+    if out.numel() != n_seg + 3 or partial.numel() < n_chunk or partial_nf.numel() < n_chunk:
+        raise RuntimeError("grad_norms: out needs n_seg + 3 values, partial / partial_nf n_chunk each")
+    a = GradNorms()
+    a.g = _cptr(g, torch.float32)
+    a.seg_off, a.seg_len = _cptr(seg_off, torch.int64), _cptr(seg_len, torch.int64)
+    a.chunk_seg, a.chunk_off, a.chunk_len = _cptr(chunk_seg, torch.int32), _cptr(chunk_off, torch.int64), _cptr(chunk_len, torch.int32)
+    a.partial, a.partial_nf = _cptr(partial, torch.float64), _cptr(partial_nf, torch.int32)
+    base = _cptr(out, torch.float32)
+    a.norms, a.total, a.coef, a.nonfinite = base, base + 4 * n_seg, base + 4 * (n_seg + 1), base + 4 * (n_seg + 2)
+    a.n, a.n_seg, a.n_chunk, a.chunk_max, a.norm_type = g.numel(), n_seg, n_chunk, int(chunk_max), int(norm_type)
+    a.max_norm = float(max_norm) if max_norm is not None and max_norm > 0 else 0.0
+    return a
+
+
+def grad_norms_launch(a: "GradNorms") -> None:
+    """tbx_grad_norms (include/tbx_hip_grad.h, libtbx_grad.so) on the current stream: two launches, a third when a.max_norm > 0. No host
+    read."""
+    _check(load_grad().tbx_grad_norms(C.byref(a), stream_ptr()), "tbx_grad_norms")

@@ -8,6 +8,7 @@ Replaces Lightning's `strategy="ddp"` (run.py:50-52) for this path. Differences 
     peers a single large message amortises launch latency best; it is ~1 % of a training step, so it is not overlapped
     with backward (nothing to hide).
 """
+import math
 import os
 import threading
 from typing import Dict, Iterable, List, Optional
@@ -15,6 +16,56 @@ from typing import Dict, Iterable, List, Optional
 import torch
 import torch.distributed as dist
 from torch import Tensor
+
+
+def grad_norm_type(track_grad_norm) -> Optional[float]:
+    """Lightning's `track_grad_norm` (trainer/default.yaml:14) -> the norm type as a float, None for -1 (off). 2, 2.0, "2", "inf" and
+    float("inf") are accepted; the other p-norms are not implemented."""
+    if track_grad_norm is None:
+        return None
+    nt = float(track_grad_norm)
+    if nt == -1.0:
+        return None
+    if nt not in (2.0, math.inf):
+        raise NotImplementedError(f"track_grad_norm={track_grad_norm!r}: only the 2-norm and the inf-norm are implemented")
+    return nt
+
+
+class GradNormPlan:
+    """The static layout tbx_grad_norms reads (include/tbx_hip_grad.h), built once per FlatGrads: the segment table (one segment per
+    parameter), the chunk table (every segment cut into consecutive chunks of at most GRAD_CHUNK elements; gaps of an aligned layout
+    are in no chunk), the two workspaces, and the parameters' names."""
+
+    def __init__(self, offsets: List[int], lengths: List[int], device, chunk: int) -> None:
+        chunk_seg, chunk_off, chunk_len = [], [], []
+        for s, (o, k) in enumerate(zip(offsets, lengths)):
+            for c in range(0, k, chunk):
+                chunk_seg.append(s), chunk_off.append(o + c), chunk_len.append(min(chunk, k - c))
+        put = lambda v, dt: torch.tensor(v, dtype=dt).to(device)
+        self.seg_off, self.seg_len = put(offsets, torch.int64), put(lengths, torch.int64)
+        self.chunk_seg, self.chunk_off, self.chunk_len = put(chunk_seg, torch.int32), put(chunk_off, torch.int64), put(chunk_len, torch.int32)
+        self.n_seg, self.n_chunk, self.chunk_max = len(offsets), len(chunk_seg), max(chunk_len, default=0)
+        self.partial = torch.empty(self.n_chunk, dtype=torch.float64, device=device)
+        self.partial_nf = torch.empty(self.n_chunk, dtype=torch.int32, device=device)
+        self.names, self.named_for = [str(i) for i in range(self.n_seg)], None  # (FlatGrads.norm_plan(module) puts the module's names in)
+
+
+class GradNormResult:
+    """What one tracking call leaves, all on the device and none read by the host: per_param f32 [n_params] (in the order of `names`),
+    total f32 [], nonfinite i32 [] (NaN / Inf gradient elements), coef f32 [] (clip_grad_norm_'s coefficient; 1 without clipping)."""
+
+    def __init__(self, per_param: Tensor, total: Tensor, nonfinite: Tensor, coef: Tensor, names: List[str], norm_type: float) -> None:
+        self.per_param, self.total, self.nonfinite, self.coef, self.names, self.norm_type = per_param, total, nonfinite, coef, names, norm_type
+
+    def as_dict(self) -> Dict[str, Tensor]:
+        """The dictionary Lightning 1.5.8's `grad_norm` utility hands to `log_grad_norm`: `grad_2.0_norm/<name>` per parameter with a
+        gradient and `grad_2.0_norm_total` (`grad_inf_norm...` for the inf norm). The values are 0-d VIEWS of the device vector - not
+        the floats rounded to 4 decimals that `.item()` would cost a host read for."""
+        pre = f"grad_{float(self.norm_type)}_norm"
+        out = {f"{pre}/{k}": v for k, v in zip(self.names, self.per_param.unbind(0))}
+        if out:
+            out[f"{pre}_total"] = self.total
+        return out
 
 
 def live_parameters(module: torch.nn.Module) -> List[torch.nn.Parameter]:
@@ -47,6 +98,7 @@ class FlatGrads:
             if p.grad is not None:
                 v.copy_(p.grad)
             self.views.append(v)
+        self._plan: Optional[GradNormPlan] = None
         self.attach()
 
     def attach(self) -> None:
@@ -78,6 +130,37 @@ class FlatGrads:
     @property
     def nbytes(self) -> int:
         return self.flat.numel() * self.flat.element_size()
+
+    def norm_plan(self, module: Optional[torch.nn.Module] = None) -> GradNormPlan:
+        """The cached GradNormPlan of this layout (tables on the buffer's device). With a module: the key list becomes the parameters'
+        names as `module.named_parameters()` gives them (`model.`-prefixed when the module is the WaymoMotion, as under Lightning)."""
+        if self._plan is None:
+            from ..abi import GRAD_CHUNK
+
+            self._plan = GradNormPlan(list(self.offsets), [p.numel() for p in self.params], self.flat.device, GRAD_CHUNK)
+        if module is not None and self._plan.named_for is not module:  # (once per module: named_parameters() walks the whole tree)
+            name_of = {id(p): k for k, p in module.named_parameters()}
+            missing = [i for i, p in enumerate(self.params) if id(p) not in name_of]
+            if missing:
+                raise KeyError(f"FlatGrads.norm_plan: {len(missing)} live parameters are not parameters of the module (first: index {missing[0]})")
+            self._plan.names, self._plan.named_for = [name_of[id(p)] for p in self.params], module
+        return self._plan
+
+    def norms(self, norm_type: float = 2.0, max_norm: Optional[float] = None) -> GradNormResult:
+        """One tbx_grad_norms call on the buffer: every parameter's gradient norm, their total, the non-finite count and
+        clip_grad_norm_'s coefficient; with max_norm > 0 the buffer is scaled by it in place. Two launches (three with the clip), no
+        atomics, no host read: capturable, and two calls on the same gradients are bit-equal."""
+        from .. import hip
+
+        nt = grad_norm_type(norm_type)
+        if nt is None:
+            raise ValueError("FlatGrads.norms: norm_type -1 is 'off'")
+        plan, n = self.norm_plan(), len(self.params)
+        out = torch.empty(n + 3, dtype=torch.float32, device=self.flat.device)  # norms | total | coef | nonfinite (i32)
+        hip.grad_norms_launch(hip.grad_norms_args(self.flat, plan.seg_off, plan.seg_len, plan.chunk_seg, plan.chunk_off, plan.chunk_len,
+                                                  plan.chunk_max, plan.partial, plan.partial_nf, out,
+                                                  hip.GRAD_NORM_2 if nt == 2.0 else hip.GRAD_NORM_INF, max_norm))
+        return GradNormResult(out[:n], out[n], out[n + 2:].view(torch.int32)[0], out[n + 1], plan.names, nt)
 
     def allreduce(self, world_size: Optional[int] = None, group=None) -> int:
         """Average across ranks, in place: one all-reduce on the buffer (RCCL over xGMI) + one scale. Returns the bytes exchanged."""
@@ -154,9 +237,15 @@ class FlatAdamW:
         torch.autograd.graph.increment_version(self.grads.params)
 
 
-def clip_gradients(params, max_norm: float):
+def clip_gradients(params, max_norm: float, track=None, module: Optional[torch.nn.Module] = None):
     """torch.nn.utils.clip_grad_norm_ (trainer/default.yaml:13 gradient_clip_val). With a FlatGrads the gradients ARE one buffer: its
-    2-norm is the norm of the per-tensor norms, and one in-place scale replaces the foreach passes over ~700 tensors (4 launches)."""
+    2-norm is the norm of the per-tensor norms, and one in-place scale replaces the foreach passes over ~700 tensors (4 launches).
+    track (a norm type: 2 or "inf"; None = off, the statements below as they always were): Lightning's track_grad_norm as well - the
+    norms of the gradients BEFORE the clip, then the clip - returned as a GradNormResult whose keys are `module`'s parameter names. On
+    a FlatGrads that is one FlatGrads.norms call (tbx_grad_norms); a plain parameter list (train_step's first eager step) takes
+    torch's multi-tensor norms."""
+    if track is not None:
+        return _track_and_clip(params, max_norm, grad_norm_type(track), module)
     if not (max_norm and max_norm > 0):
         return None
     if isinstance(params, FlatGrads):
@@ -164,6 +253,24 @@ def clip_gradients(params, max_norm: float):
         params.flat.mul_((max_norm / (total + 1e-6)).clamp(max=1.0))  # (clip_grad_norm_'s coefficient)
         return total
     return torch.nn.utils.clip_grad_norm_(params, max_norm)
+
+
+def _track_and_clip(params, max_norm, nt: float, module: Optional[torch.nn.Module]) -> GradNormResult:
+    clip = max_norm if (max_norm and max_norm > 0) else None
+    if isinstance(params, FlatGrads):
+        params.norm_plan(module)
+        return params.norms(nt, clip)
+    params = [p for p in params if p.grad is not None]
+    name_of = {id(p): k for k, p in module.named_parameters()} if module is not None else {}
+    names = [name_of.get(id(p), str(i)) for i, p in enumerate(params)]
+    grads = [p.grad for p in params]
+    per = torch.stack(torch._foreach_norm(grads, nt))
+    total = torch.linalg.vector_norm(per, nt)
+    nonfinite = (~torch.isfinite(torch.cat([g.reshape(-1) for g in grads]))).sum().to(torch.int32)
+    coef = (clip / (total + 1e-6)).clamp(max=1.0) if clip is not None else torch.ones_like(total)
+    if clip is not None:
+        torch._foreach_mul_(grads, coef)
+    return GradNormResult(per, total, nonfinite, coef, names, nt)
 
 
 def allreduce_gradients(params, world_size: Optional[int] = None, group=None) -> int:
@@ -228,11 +335,26 @@ def parameters_checksum(module: torch.nn.Module) -> Tensor:
     return torch.stack([flat.sum(), (flat * flat).sum()])
 
 
+def clip_and_track(wm, params, clip_grad_norm: float, track: Optional[float]) -> None:
+    """The clip of a training step; with tracking on (track = grad_norm_type(track_grad_norm)) Lightning's order around it: the norms of
+    the all-reduced gradients first (on_before_optimizer_step), handed to `wm.log_grad_norm`, then the clip. The result stays on
+    `wm.last_grad_norms` for callers without a logger."""
+    if track is None:
+        clip_gradients(params, clip_grad_norm)
+        return
+    res = clip_gradients(params, clip_grad_norm, track=track, module=wm)
+    wm.last_grad_norms = res
+    wm.log_grad_norm(res.as_dict())
+
+
 def train_step(wm, optimizer: torch.optim.Optimizer, batch: Dict[str, Tensor], clip_grad_norm: float = 5.0,
-               live=None) -> Dict[str, Tensor]:
+               live=None, track_grad_norm=-1) -> Dict[str, Tensor]:
     """fwd + bwd + gradient all-reduce + clip (trainer/default.yaml:13 gradient_clip_val 5.0) + optimizer step.
     live: None (first step: the live parameters are found after the backward), a list of parameters, or a FlatGrads over them
-    (gradients accumulate into its buffer, which is what travels)."""
+    (gradients accumulate into its buffer, which is what travels).
+    track_grad_norm: Lightning's argument (trainer/default.yaml:14: 2). -1 = off; 2, 2.0 or "inf": every live parameter's gradient norm
+    and the total, after the all-reduce and before the clip, go to `wm.log_grad_norm` (clip_and_track)."""
+    track = grad_norm_type(track_grad_norm)
     optimizer.zero_grad(set_to_none=True)  # (the parameters without a gradient path stay None; the live ones are handed theirs)
     loss = wm.training_step(batch, 0)
     from ..train_graph import backward_pack_scope
@@ -243,7 +365,7 @@ def train_step(wm, optimizer: torch.optim.Optimizer, batch: Dict[str, Tensor], c
         live.gather()
     params = live if live is not None else live_parameters(wm.model)
     allreduce_gradients(params)
-    clip_gradients(params, clip_grad_norm)
+    clip_and_track(wm, params, clip_grad_norm, track)
     optimizer.step()
     return wm.last_metrics
 
@@ -264,6 +386,9 @@ class GraphedTrainStep:
 
     Re-capture when the epoch changes (TeacherForcing's schedules read `current_epoch` on the host).
 
+    track_grad_norm (Lightning's argument; -1 = off): as in `train_step`, the per-parameter gradient norms are taken with the clip, in
+    the eager part between the exchange and the optimizer step (clip_and_track: one tbx_grad_norms call on the static flat buffer).
+
     ROCm caveat (7.0.x, measured with tools/hipgraph_memset_repro.py): on the runtime's AQL-packet fast path hipGraph memset nodes
     are not ordered with the kernels around them, and torch's multi-block reductions zero their semaphores with one - a
     replay then returns bias gradients of the PREVIOUS replay. `DEBUG_CLR_GRAPH_PACKET_CAPTURE=0` (read when HIP initialises)
@@ -271,7 +396,8 @@ class GraphedTrainStep:
     """
 
     def __init__(self, wm, optimizer: torch.optim.Optimizer, example_batch: Dict[str, Tensor], clip_grad_norm: float = 5.0,
-                 warmup: int = 2, verbose: bool = False) -> None:
+                 warmup: int = 2, verbose: bool = False, track_grad_norm=-1) -> None:
+        self.track = grad_norm_type(track_grad_norm)  # (as train_step's: the norms are taken eagerly, between the exchange and the clip)
         if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") != "0":
             raise RuntimeError("GraphedTrainStep needs DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 in the environment before HIP "
                                "initialises (hipGraph memset nodes replay out of order otherwise: stale gradients)")
@@ -415,7 +541,7 @@ class GraphedTrainStep:
         self.graph.replay()
         self.flat.attach()  # a zero_grad(set_to_none=True) elsewhere must not detach the static buffer's views
         allreduce_gradients(self.flat)
-        clip_gradients(self.flat, self.clip)
+        clip_and_track(self.wm, self.flat, self.clip, self.track)
         if self.flat_opt is not None and self.flat_opt.opt is self.opt:
             self.flat_opt.step()
         else:  # (not a fused AdamW on the device, or the caller has swapped the optimizer)

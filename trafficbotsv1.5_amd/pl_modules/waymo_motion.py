@@ -56,6 +56,10 @@ except Exception:  # pragma: no cover
         def log(self, k, v, **kw):
             self.logged[k] = v
 
+        def log_dict(self, dictionary, **kw):
+            for k, v in dictionary.items():
+                self.log(k, v, **kw)
+
 
 def _strip_target(cfg):
     return AttrDict({k: v for k, v in dict(cfg).items() if k != "_target_"})
@@ -418,6 +422,13 @@ class WaymoMotion(LightningModule):
             self.log(f"training/{k}", v, on_step=True)
         self.last_metrics = out
         return out["loss"]
+
+    last_grad_norms = None  # the GradNormResult of the last tracked step (data_parallel.clip_and_track), for callers without a logger
+
+    def log_grad_norm(self, grad_norm_dict: Dict[str, Tensor]) -> None:
+        """waymo_motion.py:840-841. Called with the norms of the gradients before the clip (Lightning's track_grad_norm); the values
+        are 0-d device tensors (data_parallel.GradNormResult.as_dict)."""
+        self.log_dict(grad_norm_dict, on_step=True, on_epoch=False, prog_bar=False, logger=True)
 
     # ------------------------------------------------------------------ validation
     @staticmethod
