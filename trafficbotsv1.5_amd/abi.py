@@ -2,7 +2,8 @@
 _loss.h, _tf.h), and `load()` - dlopen of the in-tree libtbx_hip.so, the one library, with every declared symbol checked and every
 prototype set. Nothing here computes; the wrappers that launch kernels are in hip.py (which re-exports this module's names).
 tests/test_abi_and_host.py compiles the header with gcc and compares every structure's `sizeof` and every field's `offsetof` with the
-classes below."""
+classes below. Two headers stand on their own, each with a library and a loader of its own: tbx_hip_grad.h (libtbx_grad.so, `load_grad()`)
+and tbx_hip_sub.h (libtbx_sub.so, `load_sub()`); their mirrors are checked by tests/test_grad_norm_host.py and tests/test_sub_records_host.py."""
 import ctypes as C
 import os
 import re
@@ -11,9 +12,11 @@ from typing import List
 
 _lib = None
 _grad_lib = None
+_sub_lib = None
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "csrc" / "libtbx_hip.so"
 GRAD_LIB_PATH = _PKG / "csrc" / "libtbx_grad.so"  # tbx_grad_norms alone (include/tbx_hip_grad.h): libtbx_hip.so's export list is ABI 7's, closed
+SUB_LIB_PATH = _PKG / "csrc" / "libtbx_sub.so"  # tbx_wosac_joint_scenes, tbx_womd_predictions (include/tbx_hip_sub.h), for the same reason
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
 
 # ---- constants mirrored from include/tbx_hip.h
@@ -227,11 +230,27 @@ class GradNorms(C.Structure):
                 + [(n, C.c_int32) for n in ("n_seg", "n_chunk", "chunk_max", "norm_type")] + [("max_norm", C.c_double)])
 
 
+class JointScenes(C.Structure):
+    """tbx_joint_scenes_t (include/tbx_hip_sub.h: libtbx_sub.so, `load_sub()`). Filled by hip.wosac_joint_scenes."""
+    _fields_ = ([(n, C.c_void_p) for n in ("pos_sim", "yaw_sim", "valid_sim", "z_sim", "object_id_sim", "pos_no_sim", "yaw_no_sim", "z_no_sim",
+                                           "valid_no_sim", "object_id_no_sim", "traj_sim", "traj_no_sim", "id_sim", "id_no_sim", "count")]
+                + [(n, C.c_int32) for n in ("n_sc", "n_k", "n_ag", "n_no_sim", "n_step", "n_hist", "step_current", "const_vel_z_sim",
+                                            "const_vel_no_sim", "pad_")])
+
+
+class WomdPred(C.Structure):
+    """tbx_womd_pred_t (include/tbx_hip_sub.h). Filled by hip.womd_predictions."""
+    _fields_ = ([(n, C.c_void_p) for n in ("trajs", "scores", "object_id", "mask_pred", "scenario_center", "scenario_yaw", "out_pos", "out_scores",
+                                           "out_object_id", "out_count")]
+                + [(n, C.c_int32) for n in ("n_sc", "n_ag", "n_mode", "n_sample")])
+
+
 RULE_COLLIDED, RULE_COLLIDED_WOSAC, RULE_RUN_ROAD_EDGE, RULE_RUN_RED_LIGHT, RULE_PASSIVE = 1, 2, 4, 8, 16
 COLLISION_MAX_AG, COLLISION_LANES = 512, 4  # TBX_COLLISION_* of include/tbx_hip_reward.h: the collision kernels' agent cap / lanes per agent
 METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
 LOSS_PARTIALS = 512  # TBX_LOSS_PARTIALS of include/tbx_hip_loss.h: tbx_loss_shape's float64 workspace
 GRAD_CHUNK, GRAD_NORM_2, GRAD_NORM_INF = 8192, 2, 0  # TBX_GRAD_* of include/tbx_hip_grad.h: tbx_grad_norms' chunk size and norm types
+SUB_MAX_OBJECTS = 1024  # TBX_SUB_MAX_OBJECTS of include/tbx_hip_sub.h: most objects per scene on a compacted axis
 
 _DECL = r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\("
 
@@ -370,4 +389,23 @@ def load_grad():
     lib.tbx_grad_norms.restype = C.c_int
     lib.tbx_grad_norms.argtypes = [C.POINTER(GradNorms), C.c_void_p]
     _grad_lib = lib
+    return lib
+
+
+def load_sub():
+    """dlopen the in-tree libtbx_sub.so (built by the same Makefile) and set the prototypes of its two entry points, tbx_wosac_joint_scenes
+    and tbx_womd_predictions (include/tbx_hip_sub.h). No GPU needed. A missing library is an error: there is no fallback path."""
+    global _sub_lib
+    if _sub_lib is not None:
+        return _sub_lib
+    if not SUB_LIB_PATH.exists():
+        raise ImportError(f"{SUB_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                          "(hipcc --offload-arch=gfx950). There is no fallback path.")
+    lib = C.CDLL(str(SUB_LIB_PATH))
+    for name, struct in (("tbx_wosac_joint_scenes", JointScenes), ("tbx_womd_predictions", WomdPred)):
+        if not hasattr(lib, name):
+            raise ImportError(f"libtbx_sub.so does not export {name}")
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
+    _sub_lib = lib
     return lib

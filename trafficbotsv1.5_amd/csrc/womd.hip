@@ -1,5 +1,6 @@
 // Post-processing of the joint futures on the device-resident rollout log (include/tbx_hip.h: tbx_womd_modes, tbx_pose_to_global).
 #include "../../include/tbx_hip.h"
+#include "pose_global_core.h"
 #include "tbx_common.h"
 
 namespace {
@@ -193,8 +194,8 @@ __global__ __launch_bounds__(WOMD_THREADS) void womd_modes_kernel(const WomdArgs
 }
 
 // ---------------------------------------------------------------------------------------------- scenario frame -> global frame
-// utils/transform_utils.py:160-171 torch_pos2global (pos @ R(yaw)^T + center) and :216-226 torch_rad2global (cast_rad(yaw + scenario_yaw),
-// :9-11: (a + pi) % (2 pi) - pi with the sign of the divisor). One thread per point; points are rows of n_t steps with ld_t steps per row.
+// torch_pos2global / torch_rad2global as pose_global_core.h states them (shared with tbx_womd_predictions of libtbx_sub.so). One thread per
+// point; points are rows of n_t steps with ld_t steps per row.
 __global__ void pose_to_global_kernel(const float* __restrict__ xy, int ld_xy, const float* __restrict__ yaw, int ld_yaw,
                                       const float* __restrict__ center, const float* __restrict__ scen_yaw, int64_t per_scene, int n_t,
                                       int ld_t, int64_t total, float* __restrict__ out_pos, float* __restrict__ out_yaw) {
@@ -204,13 +205,8 @@ __global__ void pose_to_global_kernel(const float* __restrict__ xy, int ld_xy, c
   const float th = scen_yaw[sc];
   float sn, cs;
   sincosf(th, &sn, &cs);
-  const float x = xy[src * ld_xy], y = xy[src * ld_xy + 1];
-  out_pos[i * 2] = (x * cs + y * -sn) + center[sc * 2];
-  out_pos[i * 2 + 1] = (x * sn + y * cs) + center[sc * 2 + 1];
-  const float pi = 3.14159265358979323846f, two_pi = 6.28318530717958647692f;
-  float r = fmodf((yaw[src * ld_yaw] + th) + pi, two_pi);
-  if (r < 0.f) r += two_pi;
-  out_yaw[i] = r - pi;
+  tbx::pos_to_global(xy[src * ld_xy], xy[src * ld_xy + 1], sn, cs, center[sc * 2], center[sc * 2 + 1], out_pos + i * 2, out_pos + i * 2 + 1);
+  out_yaw[i] = tbx::yaw_to_global(yaw[src * ld_yaw], th);
 }
 
 }  // namespace

@@ -4,8 +4,9 @@ role. The step right after the rollout and its rule checks (SURVEY.md §8f row 3
 kept trajectories are one C-ABI call (`tbx_filter_futures`) on the device-resident rollout log.
 
 `forward` (:66-105) continues on the device: the kept futures and the not-simulated agents' histories are moved from the scenario
-frame to the global frame by `tbx_pose_to_global`; the records keep the reference's names and shapes. `get_scenario_rollouts` (protobuf)
-is out of scope.
+frame to the global frame by `tbx_pose_to_global`; the records keep the reference's names and shapes. `get_joint_scenes` builds what
+`get_scenario_rollouts` (:103-202) fills its protobuf messages with - compaction by validity, constant-velocity extrapolation - as
+device arrays in one launch (`tbx_wosac_joint_scenes`); the messages themselves need `waymo_open_dataset` and are out of scope.
 """
 from typing import Dict
 
@@ -14,6 +15,7 @@ from torch import Tensor, nn
 
 from .. import hip
 from ..utils.buffer import RolloutBuffer
+from ..utils.submission import scenario_id_codes
 
 
 class WOSACPostProcessing(nn.Module):
@@ -59,11 +61,8 @@ class WOSACPostProcessing(nn.Module):
         pos_ns, yaw_ns = batch["history/agent_no_sim/pos"].float().contiguous(), batch["history/agent_no_sim/yaw_bbox"].float().contiguous()
         N, Th = pos_ns.shape[1:3]
         pos_no_sim, yaw_no_sim = hip.pose_to_global(pos_ns, pos_ns.shape[-1], yaw_ns, 1, center, yaw, N, Th, Th)
-        scenario_id = torch.full((n_sc, 16), -1, dtype=torch.int32)  # (wosac_post_processing.py:81-86; 16 = the longest id)
-        for i, str_id in enumerate(batch["scenario_id"]):
-            scenario_id[i, : len(str_id)] = torch.tensor([ord(c) for c in str_id], dtype=torch.int32)
         return {
-            "scenario_id": scenario_id.to(trajs.device, non_blocking=True),
+            "scenario_id": scenario_id_codes(batch["scenario_id"], trajs.device),  # (wosac_post_processing.py:81-86)
             "valid_sim": batch["history/agent/valid"],
             "pos_sim": pos_sim.view(n_sc, K, A, T, 2),
             "z_sim": batch["history/agent/pos"][..., 2:3],
@@ -76,5 +75,26 @@ class WOSACPostProcessing(nn.Module):
             "object_id_no_sim": batch["history/agent_no_sim/object_id"],
         }
 
+    @torch.no_grad()
+    def get_joint_scenes(self, wosac_data: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """What `get_scenario_rollouts` (wosac_post_processing.py:103-202) puts into its protobuf messages, as device arrays from ONE
+        launch (`tbx_wosac_joint_scenes`): per scene the objects valid at `step_current`, packed to the front in index order.
+        -> "scenario_id" (passed through), "traj_sim" [n_sc, K, n_ag, T, 4] (center_x, center_y, center_z, heading), "traj_no_sim"
+        [n_sc, n_ag_no_sim, T, 4] - stored once per scene, where the reference copies it into each of the K joint scenes -,
+        "object_id_sim" [n_sc, n_ag] / "object_id_no_sim" [n_sc, n_ag_no_sim] i64 (-1 past the count), "n_sim" / "n_no_sim" [n_sc] i32.
+        T = step_gt - step_current must be pos_sim's step count (the reference silently builds trajectories of unequal length)."""
+        pos_sim = wosac_data["pos_sim"]
+        T = self.step_gt - self.step_current
+        if pos_sim.shape[3] != T:
+            raise ValueError(f"get_joint_scenes: pos_sim has {pos_sim.shape[3]} future steps, step_gt - step_current = {T}")
+        dense = lambda k: wosac_data[k].squeeze(-1).contiguous()  # (z_* are column views of the batch's positions: [n_sc, n, Th] copies)
+        traj_sim, traj_no_sim, id_sim, id_no_sim, count = hip.wosac_joint_scenes(
+            pos_sim.contiguous(), dense("yaw_sim"), wosac_data["valid_sim"].contiguous(), dense("z_sim"), wosac_data["object_id_sim"].contiguous(),
+            wosac_data["pos_no_sim"].contiguous(), dense("yaw_no_sim"), dense("z_no_sim"), wosac_data["valid_no_sim"].contiguous(),
+            wosac_data["object_id_no_sim"].contiguous(), self.step_current, self.const_vel_z_sim, self.const_vel_no_sim)
+        return {"scenario_id": wosac_data["scenario_id"], "traj_sim": traj_sim, "traj_no_sim": traj_no_sim, "object_id_sim": id_sim,
+                "object_id_no_sim": id_no_sim, "n_sim": count[:, 0], "n_no_sim": count[:, 1]}
+
     def get_scenario_rollouts(self, wosac_data):
-        raise NotImplementedError("the protobuf submission records need waymo_open_dataset (SURVEY.md §8f)")
+        raise NotImplementedError("the protobuf submission records need waymo_open_dataset (SURVEY.md §8f); "
+                                  "get_joint_scenes(wosac_data) returns what they hold as arrays")

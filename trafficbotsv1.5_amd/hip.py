@@ -13,7 +13,7 @@ import torch
 
 from . import abi, hip_base
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
-from .abi import GRAD_LIB_PATH, HEADER_PATH, LIB_PATH, load, load_grad  # noqa: F401
+from .abi import GRAD_LIB_PATH, HEADER_PATH, LIB_PATH, SUB_LIB_PATH, load, load_grad, load_sub  # noqa: F401
 from .hip_base import *  # noqa: F401,F403  (Seg, stream_ptr, packed_weight / stacked_linear / padded_weight)
 from .hip_base import _attn_args, _check, _cptr, _fill_drop, _ptr  # noqa: F401
 from .hip_chain import *  # noqa: F401,F403  (Chain, group_tile_rows)
@@ -570,3 +570,75 @@ def grad_norms_launch(a: "GradNorms") -> None:
     """tbx_grad_norms (include/tbx_hip_grad.h, libtbx_grad.so) on the current stream: two launches, a third when a.max_norm > 0. No host
     read."""
     _check(load_grad().tbx_grad_norms(C.byref(a), stream_ptr()), "tbx_grad_norms")
+
+
+def _sub_in(t, dtype, shape, what: str, who: str):
+    """A dense device input of tbx_hip_sub.h: the given dtype (bool storage passes for u8) and shape -> its pointer (None for no elements)."""
+    if t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool):
+        raise TypeError(f"{who}: {what} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise TypeError(f"{who}: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
+    p = _cptr(t)  # (a CPU tensor raises here, an empty one too)
+    return p if t.numel() else None
+
+
+def wosac_joint_scenes(pos_sim, yaw_sim, valid_sim, z_sim, object_id_sim, pos_no_sim, yaw_no_sim, z_no_sim, valid_no_sim, object_id_no_sim,
+                       step_current: int, const_vel_z_sim: bool, const_vel_no_sim: bool, out=None):
+    """tbx_wosac_joint_scenes (include/tbx_hip_sub.h, libtbx_sub.so) on the current stream. Dense device tensors in the shapes of the
+    header's table: pos_sim [n_sc, K, A, T, 2], yaw_sim [n_sc, K, A, T], valid_sim [n_sc, A, Th] u8 / bool, z_sim [n_sc, A, Th],
+    object_id_sim [n_sc, A] i64 and the no-sim five [n_sc, N, Th(, 2)] / [n_sc, N].
+    -> (traj_sim f32 [n_sc, K, A, T, 4], traj_no_sim f32 [n_sc, N, T, 4], id_sim i64 [n_sc, A], id_no_sim i64 [n_sc, N], count i32 [n_sc, 2]);
+    out = such a tuple of a previous call: written in place (every element, whatever it held)."""
+    who = "wosac_joint_scenes"
+    if pos_sim.dim() != 5 or valid_sim.dim() != 3 or pos_no_sim.dim() != 4:
+        raise TypeError(f"{who}: pos_sim [n_sc, K, A, T, 2], valid_sim [n_sc, A, Th], pos_no_sim [n_sc, N, Th, 2]")
+    n_sc, K, A, T = pos_sim.shape[:4]
+    Th, N = valid_sim.shape[2], pos_no_sim.shape[1]
+    f32, u8, i64 = torch.float32, torch.uint8, torch.int64
+    a = JointScenes()
+    a.pos_sim, a.yaw_sim = _sub_in(pos_sim, f32, (n_sc, K, A, T, 2), "pos_sim", who), _sub_in(yaw_sim, f32, (n_sc, K, A, T), "yaw_sim", who)
+    a.valid_sim, a.z_sim = _sub_in(valid_sim, u8, (n_sc, A, Th), "valid_sim", who), _sub_in(z_sim, f32, (n_sc, A, Th), "z_sim", who)
+    a.object_id_sim = _sub_in(object_id_sim, i64, (n_sc, A), "object_id_sim", who)
+    a.pos_no_sim, a.yaw_no_sim = _sub_in(pos_no_sim, f32, (n_sc, N, Th, 2), "pos_no_sim", who), _sub_in(yaw_no_sim, f32, (n_sc, N, Th), "yaw_no_sim", who)
+    a.z_no_sim, a.valid_no_sim = _sub_in(z_no_sim, f32, (n_sc, N, Th), "z_no_sim", who), _sub_in(valid_no_sim, u8, (n_sc, N, Th), "valid_no_sim", who)
+    a.object_id_no_sim = _sub_in(object_id_no_sim, i64, (n_sc, N), "object_id_no_sim", who)
+    dev = pos_sim.device
+    if out is None:
+        out = (torch.empty(n_sc, K, A, T, 4, dtype=f32, device=dev), torch.empty(n_sc, N, T, 4, dtype=f32, device=dev),
+               torch.empty(n_sc, A, dtype=i64, device=dev), torch.empty(n_sc, N, dtype=i64, device=dev),
+               torch.empty(n_sc, 2, dtype=torch.int32, device=dev))
+    traj_sim, traj_no_sim, id_sim, id_no_sim, count = out
+    a.traj_sim, a.traj_no_sim = _sub_in(traj_sim, f32, (n_sc, K, A, T, 4), "traj_sim", who), _sub_in(traj_no_sim, f32, (n_sc, N, T, 4), "traj_no_sim", who)
+    a.id_sim, a.id_no_sim = _sub_in(id_sim, i64, (n_sc, A), "id_sim", who), _sub_in(id_no_sim, i64, (n_sc, N), "id_no_sim", who)
+    a.count = _sub_in(count, torch.int32, (n_sc, 2), "count", who)
+    a.n_sc, a.n_k, a.n_ag, a.n_no_sim, a.n_step, a.n_hist, a.step_current = n_sc, K, A, N, T, Th, int(step_current)
+    a.const_vel_z_sim, a.const_vel_no_sim = int(bool(const_vel_z_sim)), int(bool(const_vel_no_sim))
+    _check(load_sub().tbx_wosac_joint_scenes(C.byref(a), stream_ptr()), "tbx_wosac_joint_scenes")
+    return out
+
+
+def womd_predictions(trajs, scores, object_id, mask_pred, scenario_center, scenario_yaw, out=None):
+    """tbx_womd_predictions (include/tbx_hip_sub.h, libtbx_sub.so) on the current stream. trajs [n_sc, A, k, n, 3] (the "trajs" of
+    WOMDPostProcessing.forward), scores [n_sc, A, k], object_id [n_sc, A] i64, mask_pred [n_sc, A] u8 / bool, scenario_center [n_sc, 2],
+    scenario_yaw [n_sc]: dense device tensors -> (pos f32 [n_sc, A, k, n, 2] global frame, scores [n_sc, A, k], object_id i64 [n_sc, A],
+    count i32 [n_sc]), the agents with mask_pred first; out = such a tuple of a previous call: written in place."""
+    who = "womd_predictions"
+    if trajs.dim() != 5:
+        raise TypeError(f"{who}: trajs [n_sc, A, k, n, 3]")
+    n_sc, A, k, n = trajs.shape[:4]
+    f32, u8, i64 = torch.float32, torch.uint8, torch.int64
+    a = WomdPred()
+    a.trajs, a.scores = _sub_in(trajs, f32, (n_sc, A, k, n, 3), "trajs", who), _sub_in(scores, f32, (n_sc, A, k), "scores", who)
+    a.object_id, a.mask_pred = _sub_in(object_id, i64, (n_sc, A), "object_id", who), _sub_in(mask_pred, u8, (n_sc, A), "mask_pred", who)
+    a.scenario_center = _sub_in(scenario_center, f32, (n_sc, 2), "scenario_center", who)
+    a.scenario_yaw = _sub_in(scenario_yaw, f32, (n_sc,), "scenario_yaw", who)
+    dev = trajs.device
+    if out is None:
+        out = (torch.empty(n_sc, A, k, n, 2, dtype=f32, device=dev), torch.empty(n_sc, A, k, dtype=f32, device=dev),
+               torch.empty(n_sc, A, dtype=i64, device=dev), torch.empty(n_sc, dtype=torch.int32, device=dev))
+    pos, out_scores, out_id, count = out
+    a.out_pos, a.out_scores = _sub_in(pos, f32, (n_sc, A, k, n, 2), "pos", who), _sub_in(out_scores, f32, (n_sc, A, k), "scores (out)", who)
+    a.out_object_id, a.out_count = _sub_in(out_id, i64, (n_sc, A), "object_id (out)", who), _sub_in(count, torch.int32, (n_sc,), "count", who)
+    a.n_sc, a.n_ag, a.n_mode, a.n_sample = n_sc, A, k, n
+    _check(load_sub().tbx_womd_predictions(C.byref(a), stream_ptr()), "tbx_womd_predictions")
+    return out

@@ -5,8 +5,9 @@ The rollout is a device-resident state machine (utils/rollout_engine.py) replayi
 rollouts are independent, so multi-GPU inference shards them over ranks with no collective.
 `womd_post_processing` / `wosac_post_processing` (data_modules/) turn the rollout log into scored modes and global-frame records on the
 device; `validation_step` / `validation_epoch_end` run the reference's statements around them and reduce the rollout logs to the
-epoch's `val/loss`, error and traffic-rule numbers on the device (models/metrics/logging.py: tbx_rollout_metrics). WOMD / WOSAC
-metrics, submission writers and video logging of the reference are out of scope.
+epoch's `val/loss`, error and traffic-rule numbers on the device (models/metrics/logging.py: tbx_rollout_metrics); `test_step` /
+`test_epoch_end` run the reference's test loop and leave the submission records (utils/submission.py) as arrays. WOMD / WOSAC metrics,
+the protobuf submission files and video logging of the reference are out of scope.
 """
 import copy
 import dataclasses
@@ -32,6 +33,7 @@ from ..utils.buffer import RolloutBuffer
 from ..utils.dynamics import Dynamics
 from ..utils.rewards import DifferentiableReward
 from ..utils.rollout_engine import RolloutEngine, add_collision_term
+from ..utils.submission import SubWOMD, SubWOSAC
 from ..utils.teacher_forcing import TeacherForcing
 from ..utils.traffic_rule_checker import TrafficRuleChecker
 
@@ -122,6 +124,11 @@ class WaymoMotion(LightningModule):
                                                            **_strip_target(womd_post_processing))
         if wosac_post_processing:
             self.wosac_post_processing = WOSACPostProcessing(**_strip_target(wosac_post_processing))
+        # waymo_motion.py:111-114: the submission records of test_step. The sections arrive in **unused (hparams keeps them as it
+        # kept every unnamed argument); a configuration without one gets an inactive stand-in
+        self.sub_womd_joint_future_pred = SubWOMD(**(_strip_target(unused["sub_womd_joint_future_pred"])
+                                                     if unused.get("sub_womd_joint_future_pred") else {"is_active": False}))
+        self.sub_wosac = SubWOSAC(**(_strip_target(unused["sub_wosac"]) if unused.get("sub_wosac") else {"is_active": False}))
         self._engine: Optional[RolloutEngine] = None
         self._engines: "OrderedDict[tuple, RolloutEngine]" = OrderedDict()  # engines by (shapes, schedule, weights version): begin_rollout
         self.engine_cache = 2  # engines kept (least recently used dropped); 0: a fresh engine + graph capture per rollout
@@ -508,6 +515,62 @@ class WaymoMotion(LightningModule):
                 self.log(k, v, on_epoch=True)
             m.reset()
         self.log("val/loss", epoch_train_metrics_reactive_replay["reactive_replay/loss"], on_epoch=True)
+
+    # ------------------------------------------------------------------ test
+    last_womd_joint_future_pred = last_wosac_data = last_joint_scenes = None  # what the last test_step / validation_step computed
+
+    @torch.no_grad()
+    def test_step(self, batch: Dict[str, Tensor], batch_idx: int) -> None:
+        """waymo_motion.py:843-909 statement by statement, on a test-split batch (`history/*` keys, map, scenario pose and id, the
+        not-simulated agents): prior latent, destinations, `n_joint_future_wosac` joint futures, their rule rates, the WOMD modes and the
+        WOSAC records, and - where the configuration's `sub_womd_joint_future_pred` / `sub_wosac` sections are active - the submission
+        records (utils/submission.py). Results stay on `last_womd_joint_future_pred`, `last_wosac_data` and `last_joint_scenes` (the
+        joint scenes of `last_wosac_data`, computed with or without an active `sub_wosac`). The caller's `batch` dict is left as it is.
+        Needs both post-processing sections; log_val_video (:911-920) is not part of this package."""
+        with engine.use(self.schedule):
+            batch = self.pre_processing(dict(batch))
+            model = self.model
+            mp_tokens = model.mp_encoder(batch["sc/mp_valid"], batch["sc/mp_attr"], batch["sc/mp_pose"], batch["ref/mp_type"])
+            tl_tokens = model.tl_encoder.pre_compute(tl_valid=batch["sc/tl_valid"], tl_attr=batch["sc/tl_attr"], tl_pose=batch["sc/tl_pose"],
+                                                     **mp_tokens)
+            latent_prior = model.latent_encoder(ag_valid=batch["sc/ag_valid"], ag_attr=batch["sc/ag_attr"], ag_motion=batch["sc/ag_motion"],
+                                                ag_pose=batch["sc/ag_pose"], ag_type=batch["ref/ag_type"], tl_state=batch["sc/tl_state"],
+                                                mp_tokens=mp_tokens, tl_tokens=tl_tokens, posterior=False)
+            navi_pred = model.navi_predictor(ag_valid=batch["sc/ag_valid"], ag_attr=batch["sc/ag_attr"], ag_motion=batch["sc/ag_motion"],
+                                             ag_pose=batch["sc/ag_pose"], ag_type=batch["ref/ag_type"], **mp_tokens)
+            buffer_joint_future_pred = self.joint_future_pred(batch=batch, mp_tokens=mp_tokens, tl_tokens=tl_tokens, ag_latent_dist=latent_prior,
+                                                              ag_navi_dist=navi_pred, teacher_forcing=self.teacher_forcing_joint_future_pred,
+                                                              n_joint_future=self.hparams.n_joint_future_wosac)
+            self.rule_metrics_joint_future_pred.update(buffer_joint_future_pred, batch["ref/ag_type"])
+            womd_joint_future_pred = self.womd_post_processing(
+                ag_type=batch["ref/ag_type"], trajs=buffer_joint_future_pred.pred_pose[:, :, :, buffer_joint_future_pred.step_future_start:],
+                scores=buffer_joint_future_pred.log_prob)
+            if self.sub_womd_joint_future_pred.is_active:
+                self.sub_womd_joint_future_pred.update(batch, **womd_joint_future_pred)
+                gpu_dict_sync = self.sub_womd_joint_future_pred.compute()
+                if self.global_rank == 0:
+                    self.sub_womd_joint_future_pred.aggregate_on_cpu(gpu_dict_sync)
+                self.sub_womd_joint_future_pred.reset()
+            wosac_data = self.wosac_post_processing(batch, buffer_joint_future_pred)
+            if self.sub_wosac.is_active:
+                joint_scenes = self.sub_wosac.update(wosac_data, self.wosac_post_processing)
+                gpu_dict_sync = self.sub_wosac.compute()
+                if self.global_rank == 0:
+                    self.sub_wosac.aggregate_on_cpu(gpu_dict_sync)
+                self.sub_wosac.reset()
+            else:
+                joint_scenes = self.wosac_post_processing.get_joint_scenes(wosac_data)
+            self.last_womd_joint_future_pred, self.last_wosac_data, self.last_joint_scenes = womd_joint_future_pred, wosac_data, joint_scenes
+        return None
+
+    def test_epoch_end(self, outputs) -> None:
+        """waymo_motion.py:922-926: the joint futures' rule rates summed over the ranks, computed, logged, reset. The submission files
+        of :927-931 are not written here (SubWOMD / SubWOSAC.records() hold their content)."""
+        m = self.rule_metrics_joint_future_pred
+        m.sync()
+        for k, v in m.compute().items():
+            self.log(k, v, on_epoch=True)
+        m.reset()
 
     def configure_optimizers(self):
         """waymo_motion.py:820-838: AdamW, separate lr group for navi_predictor, StepLR."""

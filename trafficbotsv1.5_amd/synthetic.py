@@ -294,3 +294,77 @@ def crowd_scene(batch: Dict[str, torch.Tensor], pull: float = 0.06, size_scale: 
     out["agent/goal"][..., :2] -= shift[:, :, 0]
     out["agent/size"] *= size_scale
     return out
+
+
+def _scenario_ids(g: torch.Generator, n_sc: int):
+    """Hex scenario ids of 12 - 16 characters -> (list of str, [n_sc, 16] int32 of their characters padded with -1)."""
+    hexdigits = "0123456789abcdef"
+    ids = ["".join(hexdigits[int(c)] for c in torch.randint(0, 16, (int(n),), generator=g)) for n in torch.randint(12, 17, (n_sc,), generator=g)]
+    code = torch.full((n_sc, 16), -1, dtype=torch.int32)
+    for i, s in enumerate(ids):
+        code[i, : len(s)] = torch.tensor([ord(c) for c in s], dtype=torch.int32)
+    return ids, code
+
+
+def make_sub_case(n_sc: int = 3, n_k: int = 32, n_ag: int = 12, n_no_sim: int = 70, n_step: int = 20, n_step_hist: int = 11,
+                  step_current: int = 10, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded `wosac_data` as `WOSACPostProcessing.forward` returns it (the reference's keys, shapes and dtypes, global frame), made to
+    exercise the joint-scene records: scenes a few km from the origin, non-zero z velocities for simulated and not-simulated objects,
+    ragged validity - about 70 % of the objects valid at `step_current`, a third of those not at the step before (no velocity) -, and,
+    with three scenes or more, scene 1 without a valid not-simulated object and scene 2 without a valid simulated agent."""
+    g = torch.Generator().manual_seed(60_000 + seed)
+    U = lambda *s: torch.rand(*s, generator=g)
+    c, Th = step_current, n_step_hist
+    center = (U(n_sc, 1, 1, 2) - 0.5) * 1.6e4
+    t_hist = torch.arange(Th, dtype=torch.float32).view(1, 1, Th, 1)
+
+    def objects(n):
+        valid = U(n_sc, n, Th) < 0.8
+        valid[..., c] = U(n_sc, n) < 0.7
+        valid[..., c - 1] &= U(n_sc, n) < 0.67
+        pos = center + (U(n_sc, n, 1, 2) - 0.5) * 300.0 + (U(n_sc, n, 1, 2) - 0.5) * 2.0 * t_hist
+        z = U(n_sc, n, 1, 1) * 30.0 + (U(n_sc, n, 1, 1) - 0.5) * 0.2 * t_hist + torch.randn(n_sc, n, Th, 1, generator=g) * 0.01
+        yaw = (U(n_sc, n, Th, 1) - 0.5) * 2 * math.pi
+        return valid, pos, z, yaw
+
+    valid_sim, _, z_sim, _ = objects(n_ag)
+    valid_ns, pos_ns, z_ns, yaw_ns = objects(n_no_sim)
+    if n_sc >= 3:
+        valid_ns[1, :, c] = False
+        valid_sim[2, :, c] = False
+    ids = torch.stack([torch.randperm(4 * (n_ag + n_no_sim), generator=g) for _ in range(n_sc)])
+    return {
+        "scenario_id": _scenario_ids(g, n_sc)[1],
+        "valid_sim": valid_sim,
+        "pos_sim": center.unsqueeze(1) + (U(n_sc, n_k, n_ag, n_step, 2) - 0.5) * 300.0,
+        "z_sim": z_sim,
+        "yaw_sim": (U(n_sc, n_k, n_ag, n_step, 1) - 0.5) * 2 * math.pi,
+        "valid_no_sim": valid_ns,
+        "object_id_sim": ids[:, :n_ag].clone(),
+        "pos_no_sim": pos_ns,
+        "z_no_sim": z_ns,
+        "yaw_no_sim": yaw_ns,
+        "object_id_no_sim": ids[:, n_ag:n_ag + n_no_sim].clone(),
+    }
+
+
+def make_womd_sub_case(n_sc: int = 3, n_ag: int = 12, k: int = 6, n: int = 16, seed: int = 0) -> Dict[str, object]:
+    """Seeded inputs of `SubWOMD.update`: "trajs" [n_sc, n_ag, k, n, 3] / "scores" [n_sc, n_ag, k] as `WOMDPostProcessing.forward` returns
+    them (scenario frame) and the batch keys it reads - scenario pose a few km out, string ids, object ids, `ref/ag_role` whose column 2
+    marks the agents to predict: about half of them, none in scene 1 and all in scene 2 (with three scenes or more)."""
+    g = torch.Generator().manual_seed(70_000 + seed)
+    U = lambda *s: torch.rand(*s, generator=g)
+    role = U(n_sc, n_ag, 3) < 0.5
+    if n_sc >= 3:
+        role[1, :, 2] = False
+        role[2, :, 2] = True
+    scores = U(n_sc, n_ag, k) + 0.05
+    return {
+        "trajs": torch.cat([(U(n_sc, n_ag, k, n, 2) - 0.5) * 200.0, (U(n_sc, n_ag, k, n, 1) - 0.5) * 2 * math.pi], -1),
+        "scores": scores / scores.sum(-1, keepdim=True),
+        "scenario_center": (U(n_sc, 2) - 0.5) * 2.0e4,
+        "scenario_yaw": (U(n_sc) - 0.5) * 2 * math.pi,
+        "scenario_id": _scenario_ids(g, n_sc)[0],
+        "history/agent/object_id": torch.stack([torch.randperm(4 * n_ag, generator=g)[:n_ag] for _ in range(n_sc)]),
+        "ref/ag_role": role,
+    }
