@@ -3,7 +3,8 @@ _loss.h, _tf.h), and `load()` - dlopen of the in-tree libtbx_hip.so, the one lib
 prototype set. Nothing here computes; the wrappers that launch kernels are in hip.py (which re-exports this module's names).
 tests/test_abi_and_host.py compiles the header with gcc and compares every structure's `sizeof` and every field's `offsetof` with the
 classes below. Two headers stand on their own, each with a library and a loader of its own: tbx_hip_grad.h (libtbx_grad.so, `load_grad()`)
-and tbx_hip_sub.h (libtbx_sub.so, `load_sub()`); their mirrors are checked by tests/test_grad_norm_host.py and tests/test_sub_records_host.py."""
+and tbx_hip_sub.h (libtbx_sub.so, `load_sub()`); their mirrors are checked by tests/test_grad_norm_host.py and tests/test_sub_records_host.py.
+tbx_hip_aggr.h (libtbx_aggr.so, `load_aggr()`) is a third of that kind: tests/test_womd_aggr_host.py."""
 import ctypes as C
 import os
 import re
@@ -13,10 +14,12 @@ from typing import List
 _lib = None
 _grad_lib = None
 _sub_lib = None
+_aggr_lib = None
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "csrc" / "libtbx_hip.so"
 GRAD_LIB_PATH = _PKG / "csrc" / "libtbx_grad.so"  # tbx_grad_norms alone (include/tbx_hip_grad.h): libtbx_hip.so's export list is ABI 7's, closed
 SUB_LIB_PATH = _PKG / "csrc" / "libtbx_sub.so"  # tbx_wosac_joint_scenes, tbx_womd_predictions (include/tbx_hip_sub.h), for the same reason
+AGGR_LIB_PATH = _PKG / "csrc" / "libtbx_aggr.so"  # tbx_womd_aggr alone (include/tbx_hip_aggr.h), for the same reason
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
 
 # ---- constants mirrored from include/tbx_hip.h
@@ -245,12 +248,21 @@ class WomdPred(C.Structure):
                 + [(n, C.c_int32) for n in ("n_sc", "n_ag", "n_mode", "n_sample")])
 
 
+class WomdAggr(C.Structure):
+    """tbx_womd_aggr_t (include/tbx_hip_aggr.h: the one entry point of libtbx_aggr.so, `load_aggr()`). Filled by hip.womd_aggr."""
+    _fields_ = ([(n, C.c_void_p) for n in ("pred_pose", "log_prob", "ag_type", "out_trajs", "out_scores", "out_idx")]
+                + [(n, C.c_int32) for n in ("n_scene", "n_k", "n_ag", "ld_t", "t_start", "n_step", "k_pred", "use_ade", "n_iter_em",
+                                            "sample_first", "sample_stride", "sample_end", "has_mpa")]
+                + [("aggr_thresh", C.c_float * 3), ("mpa_nms_thresh", C.c_float * 3), ("score_temperature", C.c_float)])
+
+
 RULE_COLLIDED, RULE_COLLIDED_WOSAC, RULE_RUN_ROAD_EDGE, RULE_RUN_RED_LIGHT, RULE_PASSIVE = 1, 2, 4, 8, 16
 COLLISION_MAX_AG, COLLISION_LANES = 512, 4  # TBX_COLLISION_* of include/tbx_hip_reward.h: the collision kernels' agent cap / lanes per agent
 METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
 LOSS_PARTIALS = 512  # TBX_LOSS_PARTIALS of include/tbx_hip_loss.h: tbx_loss_shape's float64 workspace
 GRAD_CHUNK, GRAD_NORM_2, GRAD_NORM_INF = 8192, 2, 0  # TBX_GRAD_* of include/tbx_hip_grad.h: tbx_grad_norms' chunk size and norm types
 SUB_MAX_OBJECTS = 1024  # TBX_SUB_MAX_OBJECTS of include/tbx_hip_sub.h: most objects per scene on a compacted axis
+AGGR_MAX_K, AGGR_MAX_KEEP, AGGR_MAX_T = 128, 8, 91  # TBX_AGGR_* of include/tbx_hip_aggr.h: tbx_womd_aggr's futures, modes and steps
 
 _DECL = r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\("
 
@@ -408,4 +420,22 @@ def load_sub():
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(struct), C.c_void_p]
     _sub_lib = lib
+    return lib
+
+
+def load_aggr():
+    """dlopen the in-tree libtbx_aggr.so (built by the same Makefile) and set the prototype of its one entry point, tbx_womd_aggr
+    (include/tbx_hip_aggr.h). No GPU needed. A missing library is an error: there is no fallback path."""
+    global _aggr_lib
+    if _aggr_lib is not None:
+        return _aggr_lib
+    if not AGGR_LIB_PATH.exists():
+        raise ImportError(f"{AGGR_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                          "(hipcc --offload-arch=gfx950). There is no fallback path.")
+    lib = C.CDLL(str(AGGR_LIB_PATH))
+    if not hasattr(lib, "tbx_womd_aggr"):
+        raise ImportError("libtbx_aggr.so does not export tbx_womd_aggr")
+    lib.tbx_womd_aggr.restype = C.c_int
+    lib.tbx_womd_aggr.argtypes = [C.POINTER(WomdAggr), C.c_void_p]
+    _aggr_lib = lib
     return lib

@@ -7,7 +7,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
-from .abi import load  # noqa: F401
+from .abi import load, load_aggr  # noqa: F401
 from .hip_base import _check, _cptr, _ptr, stream_ptr
 
 
@@ -136,6 +136,39 @@ def womd_modes(pred_pose, log_prob, ag_type_u8, n_scene: int, n_k: int, t_start:
                                A, ld_t, t_start, n_step, k_pred, int(bool(use_ade)), mtr, mpa, float(score_temperature), sample_first,
                                sample_stride, sample_end, _ptr(trajs), _ptr(scores), _ptr(idx), stream_ptr())
     _check(rc, "tbx_womd_modes")
+    return trajs, scores, idx
+
+
+def womd_aggr(pred_pose, log_prob, ag_type_u8, n_scene: int, n_k: int, t_start: int, n_step: int, k_pred: int, use_ade: bool,
+              aggr_thresh: Sequence[float], n_iter_em: int, mpa_nms_thresh: Optional[Sequence[float]] = None,
+              score_temperature: float = -1.0, sample_first: int = 4, sample_stride: int = 5, sample_end: Optional[int] = None):
+    """tbx_womd_aggr (include/tbx_hip_aggr.h, libtbx_aggr.so) on the rollout log in place: `womd_modes`' arguments and view checks, with
+    aggr_thresh [veh, ped, cyc] and n_iter_em in place of mtr_nms_thresh; n_k > k_pred.
+    -> (trajs [n_scene, A, k_pred, n_out, 3] the cluster means, scores [n_scene, A, k_pred], idx [n_scene, A, k_pred] i32 the seeds)."""
+    R, A, T_avail = pred_pose.shape[:3]
+    ld_t = log_row_steps(pred_pose) if pred_pose.dim() == 4 else None
+    if ld_t is None or R != n_scene * n_k or t_start + n_step > T_avail:
+        raise RuntimeError("womd_aggr: pred_pose must be [n_scene*n_k, A, T, 3] rows of the rollout log (dense but for the row length)")
+    aggr, mpa = _thresh3(aggr_thresh, "aggr_thresh"), _thresh3(mpa_nms_thresh, "mpa_nms_thresh")
+    if aggr is None:
+        raise ValueError("aggr_thresh: expected [veh, ped, cyc], got none (without it the call is womd_modes)")
+    sample_end = n_step if sample_end is None else min(sample_end, n_step)
+    n_out = len(range(sample_first, sample_end, sample_stride))
+    dev = pred_pose.device
+    a = WomdAggr()
+    a.pred_pose, a.log_prob, a.ag_type = _ptr(pred_pose, torch.float32), _cptr(log_prob, torch.float32), _cptr(ag_type_u8, torch.uint8)
+    trajs = torch.empty(n_scene, A, k_pred, n_out, 3, dtype=torch.float32, device=dev)
+    scores = torch.empty(n_scene, A, k_pred, dtype=torch.float32, device=dev)
+    idx = torch.empty(n_scene, A, k_pred, dtype=torch.int32, device=dev)
+    a.out_trajs, a.out_scores, a.out_idx = _ptr(trajs), _ptr(scores), _ptr(idx)
+    a.n_scene, a.n_k, a.n_ag, a.ld_t, a.t_start, a.n_step, a.k_pred = n_scene, n_k, A, ld_t, t_start, n_step, k_pred
+    a.use_ade, a.n_iter_em, a.has_mpa = int(bool(use_ade)), int(n_iter_em), int(mpa is not None)
+    a.sample_first, a.sample_stride, a.sample_end = sample_first, sample_stride, sample_end
+    a.aggr_thresh = aggr
+    if mpa is not None:
+        a.mpa_nms_thresh = mpa
+    a.score_temperature = float(score_temperature)
+    _check(load_aggr().tbx_womd_aggr(C.byref(a), stream_ptr()), "tbx_womd_aggr")
     return trajs, scores, idx
 
 

@@ -241,6 +241,36 @@ def make_womd_case(n_sc: int = 4, n_k: int = 32, n_ag: int = 64, n_step: int = 8
     return {"trajs": trajs, "log_prob": log_prob, "ag_type": ag_type}
 
 
+def make_womd_repair_case(n_ag: int = 16, n_step: int = 80, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded inputs of `WOMDPostProcessing.forward` that empty a cluster of `traj_aggr`'s k-means (`make_womd_case` almost never
+    does): one scene, 13 straight-line futures per agent that end at `REPAIR_ENDS` along one axis, x_t = end (t + 1) / T. The first six
+    carry the high log-probabilities and become the seeds. Round 1 gives the seed at 0 the futures at 1.9 and -19 .. -19.4 and the seed at
+    -40 those at -22 .. -22.6; the means move to -11.1 and -26.7, so in round 2 the futures at 0 and 1.9 go to the seed at 4, those
+    at -19 .. -19.4 to the cluster around -26.7: the first cluster is empty and the cluster of seven gives up three. Per agent a random
+    permutation of the futures, a scale in [0.5, 2], a random heading, lateral jitter 0.05 N(0,1) (t + 1) / T and yaw = heading +
+    0.01 N(0,1) per future; random one-hot types, every fourth agent without one.
+    -> trajs [1, 13, A, T, 3] (x, y, yaw), log_prob [1, 13, A], ag_type [1, A, 3] bool."""
+    ends = torch.tensor([0.0, 4.0, -40.0, 100.0, 200.0, 300.0, 1.9, -19.0, -19.2, -19.4, -22.0, -22.3, -22.6])
+    n_k = ends.numel()
+    logp = torch.cat([-0.1 * torch.arange(6, dtype=torch.float32), -8.0 - 0.1 * torch.arange(n_k - 6, dtype=torch.float32)])
+    g = torch.Generator().manual_seed(40_000 + seed)
+    ramp = torch.arange(1, n_step + 1, dtype=torch.float32) / n_step  # [T]
+    trajs, log_prob = torch.empty(1, n_k, n_ag, n_step, 3), torch.empty(1, n_k, n_ag)
+    for a in range(n_ag):
+        perm = torch.randperm(n_k, generator=g)
+        scale = 0.5 + 1.5 * float(torch.rand((), generator=g))
+        head = (float(torch.rand((), generator=g)) * 2 - 1) * math.pi
+        along = (ends[perm] * scale)[:, None] * ramp  # [K, T]
+        lat = 0.05 * torch.randn(n_k, 1, generator=g) * ramp
+        trajs[0, :, a, :, 0] = along * math.cos(head) - lat * math.sin(head)
+        trajs[0, :, a, :, 1] = along * math.sin(head) + lat * math.cos(head)
+        trajs[0, :, a, :, 2] = head + 0.01 * torch.randn(n_k, 1, generator=g)
+        log_prob[0, :, a] = logp[perm]
+    ag_type = torch.nn.functional.one_hot(torch.randint(0, 3, (1, n_ag), generator=g), 3).bool()
+    ag_type[:, 3::4] = False
+    return {"trajs": trajs, "log_prob": log_prob, "ag_type": ag_type}
+
+
 def make_wosac_keys(n_sc: int = 1, n_ag: int = 64, seed: int = 0, n_ag_no_sim: int = 256, n_step_hist: int = 11) -> Dict[str, object]:
     """The batch keys `WOSACPostProcessing.forward` reads besides those of `to_history_batch` (reference data_h5_womd.py:52-54 and
     tensor_size_test): the scenario's global pose (a few km from the origin, as in WOMD) and id, and the agents that are not simulated.
