@@ -266,7 +266,8 @@ typedef struct tbx_tl_tail {
   const float* mlp_images[3];            /* n 128 k 128, n 128 k 128, n 16 k 128 (the n_state outputs zero-padded to 16) */
   const uint8_t* tl_invalid;             /* [rows] */
   float* logits_out;                     /* [rows, n_state] */
-  int32_t ld_kv, kv_bf16, n_state, pad_;
+  int32_t ld_kv, kv_bf16, n_state, pad_; /* kv_bf16 in a tbx_knarpe_dec_layer[_pair] launch: the element type of the launch's own tables
+                                          * (mid.self_seg.kv_bf16) - one kernel per type; another one is TBX_ERR_UNSUPPORTED */
   float clamp_lo, clamp_hi;
   /* sim_state != NULL (round 6; with it `prep_*`): behind its logits the row's workgroup also runs the NEXT step of its light -
    * tbx_sim_step(sim_state, sim_parts = TBX_SIM_LIGHTS [| TBX_SIM_ADVANCE], rows) for that light alone, rows = the tbx_tl_rows_t of
@@ -301,7 +302,9 @@ int tbx_knarpe_dec_layer(const tbx_dec_layer_t* args /* host */, void* stream);
 /* TWO independent row sets as ONE launch (round 6): layer l of the agents' block and layer l of the lights' block of a closed-loop step
  * (the lights run one step ahead of the agents and read nothing of theirs) - n_a + n_b one-row workgroups on one queue instead of two
  * launches on two queues joined at every step. Both must be tail_mfma32 calls of the same kind (tail_mfma32 value, table element type,
- * relative-pose segments); either may carry its tail (heads / lights). Same results as the two single launches, bit for bit. */
+ * relative-pose segments). Same results as the two single launches, bit for bit. The tails are compiled into the kernels, and the pairs
+ * that exist are the ones a closed-loop step launches, a first: both with qkv_out (mid layers), both without a tail, a with heads and
+ * b with lights - both without or both with their sim_state; any other combination is TBX_ERR_UNSUPPORTED. */
 int tbx_knarpe_dec_layer_pair(const tbx_dec_layer_t* a /* host */, const tbx_dec_layer_t* b /* host */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -25,9 +25,14 @@ __device__ __forceinline__ void ld_unit(W& w, const float* img, int unit, int la
 constexpr int NSW = 8;  // all 8 waves sweep: a row's targets 8 per pass per wave, two waves per SIMD hide each other's load latencies
 constexpr int LO128 = 256, LO384 = 768, LO512 = 1024, LO640 = 1280;  // byte offset of the lo plane behind a K-wide hi plane
 
-// (br: the action-head branch units 22 / 23 / 24 are taken from - the agents' heads only)
-template <int N>
-__device__ __forceinline__ void issue(W& w, const MidArgs& a, bool heads, int wave, int lane, int br = 0) {
+// TAIL: the launch's tail kind (dec_mid.hip TK_*), known at compile time - a run-time choice between the tails' images puts a
+// conditional request in front of every later counted wait: at the join the wait-count pass takes the count of the path that requested
+// nothing, and the wait for a unit then also covers the units requested behind it (vmcnt retires in order).
+// br: the action-head branch units 22 / 23 / 24 are taken from - the agents' heads only; the caller clamps it (an agent without a
+// branch requests branch 0's units and never uses them: every path has the same loads in flight)
+template <int N, int TAIL>
+__device__ __forceinline__ void issue(W& w, const MidArgs& a, int wave, int lane, int br = 0) {
+  constexpr int KIND = TAIL & TK_KIND;
   if constexpr (N == 0) ld_unit(w, a.fold1, wave, lane);
   else if constexpr (N == 1) ld_unit(w, a.wo, wave, lane);
   else if constexpr (N == 2) ld_unit(w, a.wq, wave, lane);
@@ -36,25 +41,24 @@ __device__ __forceinline__ void issue(W& w, const MidArgs& a, bool heads, int wa
   else if constexpr (N == 5) ld_unit(w, a.wo2, wave, lane);
   else if constexpr (N <= 9) ld_unit(w, a.w1, 8 * (N - 6) + wave, lane);
   else if constexpr (N <= 13) ld_unit(w, a.w2, 8 * (N - 10) + wave, lane);
-  else if (a.qkv_out != nullptr) {
+  else if constexpr (KIND == TK_NEXT) {
     if constexpr (N <= 16) ld_unit(w, a.wqkv, 8 * (N - 14) + wave, lane);
     else if constexpr (N == 17) ld_unit(w, a.wqt, wave, lane);
-  } else if (a.tl.kv_out != nullptr) {  // 14..21: k, v of the agents' 4 layers; 22..24: the state predictor
+  } else if constexpr (KIND == TK_LIGHTS) {  // 14..21: k, v of the agents' 4 layers; 22..24: the state predictor
     if constexpr (N >= 14 && N <= 21) ld_unit(w, a.tl.kv_images[(N - 14) >> 1], 8 * ((N - 14) & 1) + wave, lane);
     else if constexpr (N == 22 || N == 23) ld_unit(w, a.tl.mlp_images[N - 22], wave, lane);
     else if constexpr (N == 24) ld_unit(w, a.tl.mlp_images[2], 0, lane);
-  } else if (heads) {
+  } else if constexpr (KIND == TK_HEADS) {
     if constexpr (N == 14 || N == 18) ld_unit(w, a.hw[N == 14 ? 0 : 3], wave, lane);
     else if constexpr (N == 15 || N == 19) ld_unit(w, a.hw[N == 15 ? 0 : 3], 8 + wave, lane);
     else if constexpr (N == 16 || N == 17) ld_unit(w, a.hw[N - 15], wave, lane);
     else if constexpr (N == 20 || N == 21) ld_unit(w, a.hw[N - 16], wave, lane);
-    else if constexpr (N == 22) {  // the action head's three layers of branch br (none: an invalid agent)
-      if (br >= 0) ld_unit(w, a.hw[6], 8 * br + wave, lane);
-    } else if constexpr (N == 23) {
-      if (br >= 0) ld_unit(w, a.hw[7], 8 * br + wave, lane);
-    } else if constexpr (N == 24) {
-      if (wave == 0) ld_unit(w, a.hw[8], br, lane);
-    }
+    else if constexpr (N == 22) ld_unit(w, a.hw[6], 8 * br + wave, lane);  // the action head's three layers of branch br
+    else if constexpr (N == 23) ld_unit(w, a.hw[7], 8 * br + wave, lane);
+    // (the third layer is wave 0's alone. The other waves request lane 0's 16 bytes of each fragment in its place - one cache line per
+    // load, never used - rather than nothing: behind `if (wave == 0)` the join took the count of the waves that requested nothing, and
+    // wave 0 waited for this unit a stage early, with the unit it was about to consume)
+    else if constexpr (N == 24) ld_unit(w, a.hw[8], br, wave == 0 ? lane : 0);
   }
 }
 
@@ -268,18 +272,36 @@ __device__ __forceinline__ void combine(float Mh, float Lh, const float4& o, con
   }
   __syncthreads();
 }
+// The row's LDS, declared once per KERNEL (TBX_MF_LDS) and handed to the body: a paired kernel inlines two bodies (one per half, each
+// with its own tail kind) and both work in the same 34,072 B - function-local __shared__ arrays of two instantiations would add up.
+struct Lds {
+  float (*red_s)[RED];
+  float *comb_s, *xs, *q2, *qt2, *bk2_s, *head_o;
+  char *Pc, *Ph, *Pq, *Pu, *Pv;
+  char (*Pl)[2 * LO128];  // the lights' tail: the four layers' LayerNorm planes
+};
 }  // namespace TBX_MF_NS
+#define TBX_MF_LDS(S)                                                                                                              \
+  __shared__ __attribute__((aligned(16))) float red_s[TBX_MF_NS::NSW][RED];                                                        \
+  __shared__ __attribute__((aligned(16))) float comb_s[D], xs[D], q2[D], qt2[NH * D], bk2_s[D], head_o[3 * 2];                     \
+  __shared__ __attribute__((aligned(16))) char Pc[2 * TBX_MF_NS::LO640], Ph[2 * TBX_MF_NS::LO128], Pq[2 * TBX_MF_NS::LO128],       \
+      Pu[2 * TBX_MF_NS::LO512], Pv[2 * TBX_MF_NS::LO384], Pl[4][2 * TBX_MF_NS::LO128];                                             \
+  const TBX_MF_NS::Lds S = {red_s, comb_s, xs, q2, qt2, bk2_s, head_o, Pc, Ph, Pq, Pu, Pv, Pl}
 
 // The layer of ONE row. `row` = the launch-local row index, n_wg = the workgroups that share `a` (the arrival count of the fused step
 // tails): the single launch passes (blockIdx.x, gridDim.x), the paired launch (TBX_MF_PAIR_KERNEL below) the block's index inside its half.
 // SAMP: the fused step tail with sampled actions (tbx_sim_state_t.act_seed) - kernels of their own, so that the deterministic step's
 // launches hold the tail they always had (a run-time branch inside it measured +0.6 us per step at the headline shape)
-template <bool KV16, bool REL, bool SAMP>
-__device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, const unsigned n_wg) {
+// TAIL: what follows linear2 (dec_mid.hip TK_*: nothing, the next layer's projections, the lights' tail [+ their step], the agents' heads
+// [+ the fused step tail]) - a template parameter, picked by the host entry points from the descriptors they validate; with bf16
+// tables (KV16) the next layer's bf16 k | v copy and the lights' bf16 tables are written (the entry points check that they go together).
+template <bool KV16, bool REL, bool SAMP, int TAIL>
+__device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, const unsigned n_wg, const TBX_MF_NS::Lds& lds) {
   using namespace TBX_MF_NS;
-  __shared__ __attribute__((aligned(16))) float red_s[NSW][RED];
-  __shared__ __attribute__((aligned(16))) float comb_s[D], xs[D], q2[D], qt2[NH * D], bk2_s[D], head_o[3 * 2];
-  __shared__ __attribute__((aligned(16))) char Pc[2 * LO640], Ph[2 * LO128], Pq[2 * LO128], Pu[2 * LO512], Pv[2 * LO384];
+  constexpr int KIND = TAIL & TK_KIND;
+  float(*const red_s)[RED] = lds.red_s;
+  float *const comb_s = lds.comb_s, *const xs = lds.xs, *const q2 = lds.q2, *const qt2 = lds.qt2, *const bk2_s = lds.bk2_s;
+  char *const Pc = lds.Pc, *const Ph = lds.Ph, *const Pq = lds.Pq, *const Pu = lds.Pu, *const Pv = lds.Pv;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int wir = wave;
@@ -299,9 +321,9 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
   const int g4 = lane >> 4;
   const bool col0 = (lane & 15) == 0;  // the lanes that hold column 0 = the row: channels c_out .. c_out + 3 of a 128-wide stage
   const int c_out = 16 * wave + 4 * g4;
-  const bool heads = a.hw[0] != nullptr && a.qkv_out == nullptr;
   // (the step counter of the fused tail: requested here, a round trip to memory before that tail needs it)
-  const int t_step_v = a.fused_tail ? *a.sim.step : 0;
+  int t_step_v = 0;
+  if constexpr (TAIL == (TK_HEADS | TK_SIM)) t_step_v = *a.sim.step;
   W wb[3];
   // (the row and the cross bias go to LDS behind the query-side requests: a load straight into an LDS write is waited for on the spot)
   float x_r = 0.f, bk2_r = 0.f;
@@ -342,14 +364,14 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     merge_slots_by_head(st, M, Mh, Lh, om, em);
     MID_CLK(2);
     combine(Mh, Lh, om, em, red_s, comb_s, Pc, wir, lane, s8, valid1, [&]() {
-      issue<0>(wb[0], a, heads, wave, lane);
-      issue<1>(wb[1], a, heads, wave, lane);
+      issue<0, TAIL>(wb[0], a, wave, lane);
+      issue<1, TAIL>(wb[1], a, wave, lane);
       if (wave == 0) lg1[0] = a.ln_w[lane], lg1[1] = a.ln_w[64 + lane], lb1[0] = a.ln_b[lane], lb1[1] = a.ln_b[64 + lane];
       pre_rows<KV16, REL>(a.cross, row, b, wir, s8, tg, j2, fq, pre);  // the cross sweep's first pass: in flight under the layer's middle
     });
   }
   // ---- 0: y = sum a v + W_rpe_v (sum a e) + b (wave w: head w / 2, 16 of its 32 channels)
-  issue<2>(wb[2], a, heads, wave, lane);
+  issue<2, TAIL>(wb[2], a, wave, lane);
   {
     const f32x4 y = gemv4(wb[0], Pc, LO640, 4 + 4 * (wave >> 1), g4) + wb[0].bias + *(const f32x4*)(comb_s + c_out);
     if (col0) put4(Ph, LO128, c_out, y);
@@ -357,7 +379,7 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
   __syncthreads();
   MID_CLK(3);
   // ---- 1: x += no valid target ? 0 : out_proj(y)
-  issue<3>(wb[0], a, heads, wave, lane);
+  issue<3, TAIL>(wb[0], a, wave, lane);
   {
     const f32x4 u = gemv4(wb[1], Ph, LO128, 0, g4) + wb[1].bias;
     if (col0 && valid1) *(f32x4*)(xs + c_out) = *(const f32x4*)(xs + c_out) + u;
@@ -411,24 +433,24 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     merge_slots_by_head(st, M, Mh, Lh, om, em);
     MID_CLK(9);
     combine(Mh, Lh, om, em, red_s, comb_s, Pc, wir, lane, s8, valid2, [&]() {
-      issue<4>(wb[1], a, heads, wave, lane);
-      issue<5>(wb[2], a, heads, wave, lane);
+      issue<4, TAIL>(wb[1], a, wave, lane);
+      issue<5, TAIL>(wb[2], a, wave, lane);
       if (wave == 0) {
         lg2[0] = a.ln2_w[lane], lg2[1] = a.ln2_w[64 + lane], lb2[0] = a.ln2_b[lane], lb2[1] = a.ln2_b[64 + lane];
-        if (a.qkv_out != nullptr) lg3[0] = a.ln3_w[lane], lg3[1] = a.ln3_w[64 + lane], lb3[0] = a.ln3_b[lane], lb3[1] = a.ln3_b[64 + lane];
+        if constexpr (KIND == TK_NEXT) lg3[0] = a.ln3_w[lane], lg3[1] = a.ln3_w[64 + lane], lb3[0] = a.ln3_b[lane], lb3[1] = a.ln3_b[64 + lane];
       }
     });
   }
   const bool x_valid = a.src_invalid[row] == 0;
   // ---- 4: the cross attention's value fold
-  issue<6>(wb[0], a, heads, wave, lane);
+  issue<6, TAIL>(wb[0], a, wave, lane);
   {
     const f32x4 y = gemv4(wb[1], Pc, LO640, 4 + 4 * (wave >> 1), g4) + wb[1].bias + *(const f32x4*)(comb_s + c_out);
     if (col0) put4(Ph, LO128, c_out, y);
   }
   __syncthreads();
   // ---- 5: x += no valid cross target ? 0 : out_proj2(y)
-  issue<7>(wb[1], a, heads, wave, lane);
+  issue<7, TAIL>(wb[1], a, wave, lane);
   {
     const f32x4 u = gemv4(wb[2], Ph, LO128, 0, g4) + wb[2].bias;
     if (col0 && valid2) *(f32x4*)(xs + c_out) = *(const f32x4*)(xs + c_out) + u;
@@ -441,7 +463,7 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
   // ---- 6..9: u = relu(linear1(h)), 4 rounds of 128 channels (no barrier between them: they read Ph and write disjoint parts of Pu)
 #define TBX_MF_L1(N)                                                                 \
   do {                                                                               \
-    issue<(N) + 2>(wb[((N) + 2) % 3], a, heads, wave, lane);                         \
+    issue<(N) + 2, TAIL>(wb[((N) + 2) % 3], a, wave, lane);                         \
     const W& w = wb[(N) % 3];                                                        \
     const f32x4 u = tbx_tile::relu4(gemv4(w, Ph, LO128, 0, g4) + w.bias);            \
     if (col0) put4(Pu, LO512, ((N) - 6) * D + c_out, u);                             \
@@ -459,7 +481,7 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     const f32x4 bias = wb[10 % 3].bias;
 #define TBX_MF_L2(N)                                                                 \
   do {                                                                               \
-    issue<(N) + 2>(wb[((N) + 2) % 3], a, heads, wave, lane);                         \
+    issue<(N) + 2, TAIL>(wb[((N) + 2) % 3], a, wave, lane);                         \
     const W& w = wb[(N) % 3];                                                        \
     _Pragma("unroll") for (int st = 0; st < 4; ++st) step(acc, w.hi[st], w.lo[st], Pu, LO512, 4 * ((N) - 10) + st, g4); \
   } while (0)
@@ -476,14 +498,14 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     }
   }
   MID_CLK(13);
-  if (a.qkv_out != nullptr) {
+  if constexpr (KIND == TK_NEXT) {
     // ================================================================ the next layer's projections (attention_rpe.py:92-98,147)
     __syncthreads();
     if (wave == 0) ln_planes(xs, Ph, lane, a.ln3_eps, lg3, lb3);
     __syncthreads();
     float* qrow_out = a.qkv_out + (int64_t)row * a.ld_qkv_out;
     {  // 14: q
-      issue<16>(wb[16 % 3], a, heads, wave, lane);
+      issue<16, TAIL>(wb[16 % 3], a, wave, lane);
       const W& w = wb[14 % 3];
       const f32x4 q = gemv4(w, Ph, LO128, 0, g4) + w.bias;
       if (col0) {
@@ -497,13 +519,13 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     const f32x4 kv = gemv4(w, Ph, LO128, 0, g4) + w.bias;                                             \
     if (col0) {                                                                                       \
       *(TBX_GLOBAL f32x4*)(qrow_out + ((N) - 14) * D + c_out) = kv;                                   \
-      if (a.kv16_out != nullptr) {                                                                    \
+      if constexpr (KV16) {                                                                           \
         const bf16x4 h16 = __builtin_convertvector(kv, bf16x4);                                       \
         *(TBX_GLOBAL u32x2*)(a.kv16_out + (int64_t)row * (2 * D) + ((N) - 15) * D + c_out) = __builtin_bit_cast(u32x2, h16); \
       }                                                                                               \
     }                                                                                                 \
   } while (0)
-    issue<17>(wb[17 % 3], a, heads, wave, lane);
+    issue<17, TAIL>(wb[17 % 3], a, wave, lane);
     TBX_MF_KV(15);
     TBX_MF_KV(16);
 #undef TBX_MF_KV
@@ -521,12 +543,11 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
       }
     }
     MID_CLK(15);
-    return;
   }
-  if (a.tl.kv_out != nullptr) {
+  if constexpr (KIND == TK_LIGHTS) {
     // ================================================================ the lights' tail (traffic_bots.py:188-199): the K/V rows the agents'
     // 4 layers read (emit_kv_tables: LayerNorm_l + in_proj_kv,l) and the next-state logits (traffic_light.py:249-286)
-    __shared__ __attribute__((aligned(16))) char Pl[4][2 * LO128];
+    char(*const Pl)[2 * LO128] = lds.Pl;
     __syncthreads();  // xs complete
     if (wave < 4) {   // the four layers' LayerNorms at once, a wave each
       float g[2], bt[2];
@@ -539,12 +560,12 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     const int64_t kv_row = (int64_t)row * a.tl.ld_kv;
 #define TBX_MF_TLKV(N)                                                                                    \
   do {                                                                                                    \
-    issue<(N) + 2>(wb[((N) + 2) % 3], a, heads, wave, lane);                                              \
+    issue<(N) + 2, TAIL>(wb[((N) + 2) % 3], a, wave, lane);                                              \
     const W& w = wb[(N) % 3];                                                                             \
     const f32x4 y = gemv4(w, Pl[((N) - 14) >> 1], LO128, 0, g4) + w.bias;                                 \
     if (col0) {                                                                                           \
       const int64_t o = kv_row + (((N) - 14) >> 1) * 2 * D + (((N) - 14) & 1) * D + c_out;                \
-      if (a.tl.kv_bf16) {                                                                                 \
+      if constexpr (KV16) {                                                                               \
         const bf16x4 h16 = __builtin_convertvector(y, bf16x4);                                            \
         *(TBX_GLOBAL u32x2*)((uint16_t*)a.tl.kv_out + o) = __builtin_bit_cast(u32x2, h16);                \
       } else {                                                                                            \
@@ -562,7 +583,7 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     TBX_MF_TLKV(21);
 #undef TBX_MF_TLKV
     {  // 22, 23: the predictor's hidden layers (Ph -> Pq -> Ph)
-      issue<24>(wb[24 % 3], a, heads, wave, lane);
+      issue<24, TAIL>(wb[24 % 3], a, wave, lane);
       const W& w = wb[22 % 3];
       const f32x4 h1 = tbx_tile::relu4(gemv4(w, Ph, LO128, 0, g4) + w.bias);
       if (col0) put4(Pq, LO128, c_out, h1);
@@ -586,7 +607,7 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
         }
       }
     }
-    if (a.tl_sim) {
+    if constexpr ((TAIL & TK_SIM) != 0) {
       // ============================================================ the NEXT step of this row's light (csrc/step_core.h sim_light:
       // Dynamics.override_tl on the logits just written, log, window shift, the tbx_tl_prep rows of the new window) - it reads nothing
       // of another light's. The lights' own step counter (a.sim.step) advances when the last of the launch's light rows arrives.
@@ -595,9 +616,9 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
       if (wave == 0 && lane < tbx_step::LPT) tbx_step::sim_light(a.sim, a.sim_parts, t_tl, row, lane, a.tl_prep);
       if (a.sim_parts & TBX_SIM_ADVANCE) tbx_step::sim_advance(a.sim, t_tl, n_wg);
     }
-    return;
   }
-  if (!heads) return;
+  if constexpr (KIND != TK_HEADS) return;
+  float* const head_o = lds.head_o;
   // ================================================================ the agents' heads (traffic_bots.py:206-221; csrc/tile_heads.hip's
   // stages on one row): Pv = [x | navi_emb | latent_emb] planes, the adders' hidden rows in Ph / Pq, the action head's in Pu / Pv
   if (threadIdx.x < 64) {
@@ -614,31 +635,34 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
   for (int g = 0; g < 3; ++g) act |= (a.type_mask[(int64_t)g * a.mask_stride + row] == 0 ? 1 : 0) << g;
   act = __builtin_amdgcn_readfirstlane(act);
   const int br0 = act ? __builtin_ctz((unsigned)act) : -1;
+  // (requests go out on a clamped branch: a row without a branch - or without a next one - fetches branch 0's unit and never uses it,
+  // so no request sits behind a condition and every stage's wait counts the loads really in flight)
+  const int brq0 = br0 < 0 ? 0 : br0;
   __syncthreads();
 #define TBX_MF_ADDER(N, ZSTEP, OK)                                                                    \
   do {                                                                                                \
     {                                                                                                 \
       Acc acc;                                                                                        \
       acc.zero();                                                                                     \
-      issue<(N) + 2>(wb[((N) + 2) % 3], a, heads, wave, lane, br0);                                        \
+      issue<(N) + 2, TAIL>(wb[((N) + 2) % 3], a, wave, lane, brq0);                                        \
       const W& w0 = wb[(N) % 3];                                                                      \
       const f32x4 bias = w0.bias;                                                                     \
       _Pragma("unroll") for (int st = 0; st < 4; ++st) step(acc, w0.hi[st], w0.lo[st], Pv, LO384, st, g4); \
-      issue<(N) + 3>(wb[((N) + 3) % 3], a, heads, wave, lane, br0);                                        \
+      issue<(N) + 3, TAIL>(wb[((N) + 3) % 3], a, wave, lane, brq0);                                        \
       const W& w1 = wb[((N) + 1) % 3];                                                                \
       _Pragma("unroll") for (int st = 0; st < 4; ++st) step(acc, w1.hi[st], w1.lo[st], Pv, LO384, (ZSTEP) + st, g4); \
       if (col0) put4(Ph, LO128, c_out, tbx_tile::relu4(acc.sum() + bias));                            \
     }                                                                                                 \
     __syncthreads();                                                                                  \
     {                                                                                                 \
-      issue<(N) + 4>(wb[((N) + 4) % 3], a, heads, wave, lane, br0);                                        \
+      issue<(N) + 4, TAIL>(wb[((N) + 4) % 3], a, wave, lane, brq0);                                        \
       const W& w = wb[((N) + 2) % 3];                                                                 \
       const f32x4 hdn = tbx_tile::relu4(gemv4(w, Ph, LO128, 0, g4) + w.bias);                         \
       if (col0) put4(Pq, LO128, c_out, hdn);                                                          \
     }                                                                                                 \
     __syncthreads();                                                                                  \
     {                                                                                                 \
-      issue<(N) + 5>(wb[((N) + 5) % 3], a, heads, wave, lane, br0);                                        \
+      issue<(N) + 5, TAIL>(wb[((N) + 5) % 3], a, wave, lane, brq0);                                        \
       const W& w = wb[((N) + 3) % 3];                                                                 \
       const f32x4 upd = tbx_tile::relu4(gemv4(w, Pq, LO128, 0, g4) + w.bias);                         \
       if (col0) {                                                                                     \
@@ -659,24 +683,28 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     int nx = -1;  // the next branch let through (none for a one-hot type)
     for (int g = 2; g > br; --g)
       if ((act >> g) & 1) nx = g;
+    const int nxq = nx < 0 ? 0 : nx;
     {
-      issue<24>(wb[24 % 3], a, heads, wave, lane, br);
+      issue<24, TAIL>(wb[24 % 3], a, wave, lane, br);
       const W& w = wb[22 % 3];
       const f32x4 u = tbx_tile::relu4(gemv4(w, Pv, LO384, 0, g4) + w.bias);
       if (col0) put4(Pu, LO512, br * D + c_out, u);
     }
     __syncthreads();
     {
-      issue<22>(wb[22 % 3], a, heads, wave, lane, nx);
+      issue<22, TAIL>(wb[22 % 3], a, wave, lane, nxq);
       const W& w = wb[23 % 3];
       const f32x4 u = tbx_tile::relu4(gemv4(w, Pu, LO512, 4 * br, g4) + w.bias);
       if (col0) put4(Ph, LO128, c_out, u);
     }
     __syncthreads();
-    issue<23>(wb[23 % 3], a, heads, wave, lane, nx);
+    issue<23, TAIL>(wb[23 % 3], a, wave, lane, nxq);
     if (wave == 0) {
       const W& w = wb[24 % 3];
       const f32x4 o = gemv4(w, Ph, LO128, 0, g4) + w.bias;
+      // (all four sums stay live up to here: with only o[0] and o[1] used, the bias unit's upper two registers were dead while its load
+      // was in flight, got re-used for an address a stage earlier, and that write had to wait for the load - a vmcnt(0) in the middle stage)
+      asm volatile("" ::"v"(o));
       if (lane == 0) head_o[br * 2] = o[0], head_o[br * 2 + 1] = o[1];
     }
     __syncthreads();
@@ -689,7 +717,7 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
     a.action_out[(int64_t)row * 2 + threadIdx.x] = v;
   }
   MID_CLK(14);
-  if (a.fused_tail) {
+  if constexpr ((TAIL & TK_SIM) != 0) {
     const int t_step = __builtin_amdgcn_readfirstlane(t_step_v);
     // ============================================================== the step's tail for this row's agent (csrc/step_core.h): its
     // tbx_sim_step (dynamics, rule checks, overrides, log, window append: 32 lanes) on the action just written, then the NEXT
@@ -708,36 +736,42 @@ __device__ __forceinline__ void TBX_MF_BODY(const MidArgs& a, const int row, con
   }
 }
 
-template <bool KV16, bool REL, bool SAMP>
+template <bool KV16, bool REL, bool SAMP, int TAIL>
 __global__ __launch_bounds__(512) void TBX_MF_KERNEL(const MidArgs a) {
-  TBX_MF_BODY<KV16, REL, SAMP>(a, (int)blockIdx.x, gridDim.x);
+  TBX_MF_LDS(lds);
+  TBX_MF_BODY<KV16, REL, SAMP, TAIL>(a, (int)blockIdx.x, gridDim.x, lds);
 }
 
 // TWO row sets in ONE launch (round 6: the agents' 64 and the lights' 128 one-row workgroups of layer l of a closed-loop step - the
 // lights run one step ahead of the agents and read nothing of theirs, so the two halves are independent; one launch per layer on one queue
-// instead of two queues joined at every step): blocks [0, m[0].n_rows) take m[0], the rest m[1]. The half is a scalar (blockIdx), the
+// instead of two queues joined at every step): blocks [0, n_rows[0]) take m[0], the rest m[1]. The half is a scalar (blockIdx), the
 // arguments stay in the kernel-argument segment (scalar loads at a scalar base).
 // xcd_a > 0 (tbx_knarpe_dec_layer_pair's default where both halves fit): the halves on disjoint XCDs - workgroup b runs on XCD b % 8, so
 // XCDs [0, xcd_a) take m[0]'s rows and the rest m[1]'s (slot = b / 8; a half's surplus blocks return at once): an XCD's L2 then holds ONE
 // half's weight units and K/V rows.
+// The half is resolved ONCE: what it takes - xcd_a and both row counts - leads the argument block (one scalar load), and the kernel then
+// branches into one of two inlined bodies, m[0]'s with tail TA and m[1]'s with tail TB. Every kernel-argument offset in a body is a
+// constant: with `p.m[sel]` each use of an argument was a select of two offsets, a scalar load and a wait that also covered the LDS
+// reads in flight, and the first vector load sat behind six dependent scalar round trips instead of two.
 struct TBX_MF_PAIR_ARGS {
+  int xcd_a, n_rows[2], pad_;  // n_rows[i] = m[i].n_rows
   MidArgs m[2];
-  int xcd_a;
 };
-template <bool KV16, bool REL, bool SAMP>
+template <bool KV16, bool REL, bool SAMP, int TA, int TB>
 __global__ __launch_bounds__(512) void TBX_MF_PAIR_KERNEL(const TBX_MF_PAIR_ARGS p) {
-  const int n0 = p.m[0].n_rows;
+  const int xa = p.xcd_a, n0 = p.n_rows[0], n1 = p.n_rows[1];
   int sel, row;
-  if (p.xcd_a > 0) {
+  if (xa > 0) {
     const int xcd = (int)blockIdx.x & 7, slot = (int)blockIdx.x >> 3;
-    sel = xcd >= p.xcd_a ? 1 : 0;
-    row = sel ? slot * (8 - p.xcd_a) + (xcd - p.xcd_a) : slot * p.xcd_a + xcd;
-    if (row >= (sel ? p.m[1].n_rows : n0)) return;
+    sel = xcd >= xa ? 1 : 0;
+    row = sel ? slot * (8 - xa) + (xcd - xa) : slot * xa + xcd;
+    if (row >= (sel ? n1 : n0)) return;
   } else {
     sel = (int)blockIdx.x >= n0 ? 1 : 0;
     row = (int)blockIdx.x - (sel ? n0 : 0);
   }
-  sel = __builtin_amdgcn_readfirstlane(sel);
-  const MidArgs& a = p.m[sel];
-  TBX_MF_BODY<KV16, REL, SAMP>(a, row, (unsigned)a.n_rows);
+  TBX_MF_LDS(lds);
+  if (sel == 0) TBX_MF_BODY<KV16, REL, SAMP, TA>(p.m[0], row, (unsigned)n0, lds);
+  else TBX_MF_BODY<KV16, REL, SAMP, TB>(p.m[1], row, (unsigned)n1, lds);
 }
+#undef TBX_MF_LDS

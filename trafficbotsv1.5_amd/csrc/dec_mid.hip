@@ -530,6 +530,9 @@ __global__ __launch_bounds__(NW * 64) void dec_mid_kernel(const MidArgs a) {
 // 14..16 next in_proj (q, k, v), 17 next qfold, or the heads: 14..17 add_navi (k-chunk x, k-chunk embedding, layer 2, layer 3),
 // 18..21 add_latent, 22..24 / 25..27 / 28 the action head's three stacked stages (csrc/tile_heads.hip's entries), or the lights' tail:
 // 14..21 k, v of the agents' 4 layers, 22..24 the next-state predictor, or nothing.
+// Which of these tails a launch runs is a template parameter of the kernels (TAIL = kind [| TK_SIM]), chosen by the entry points:
+constexpr int TK_NONE = 0, TK_NEXT = 1, TK_LIGHTS = 2, TK_HEADS = 3, TK_KIND = 3;
+constexpr int TK_SIM = 4;  // LIGHTS: the row's light stepped behind its logits (tl_sim); HEADS: the fused step tail (fused_tail)
 #define TBX_MF_NS mf
 #define TBX_MF_KERNEL dec_layer_mf_kernel
 #define TBX_MF_BODY dec_layer_mf_body
@@ -679,6 +682,14 @@ static int dec_fill(const tbx_dec_mid_t* p, const tbx_dec_layer_t* t, MidArgs& a
   return TBX_OK;
 }
 
+// the tail a validated launch descriptor asks for (the order dec_fill's checks leave possible: projections, lights, heads, nothing)
+static int tail_of(const MidArgs& a) {
+  if (a.qkv_out != nullptr) return TK_NEXT;
+  if (a.tl.kv_out != nullptr) return TK_LIGHTS | (a.tl_sim ? TK_SIM : 0);
+  if (a.hw[0] != nullptr) return TK_HEADS | (a.fused_tail ? TK_SIM : 0);
+  return TK_NONE;
+}
+
 static int dec_launch(const tbx_dec_mid_t* p, const tbx_dec_layer_t* t, void* stream) {
   MidArgs a;
   bool rel = false;
@@ -688,11 +699,25 @@ static int dec_launch(const tbx_dec_mid_t* p, const tbx_dec_layer_t* t, void* st
   static_assert((IMG128 + IMGKF + 4 * RED + OUTW + 8 * D) * sizeof(float) <= 160 * 1024, "LDS budget");
   hipStream_t hs = (hipStream_t)stream;
   const bool samp = a.fused_tail && (a.sim_parts & tbx_step::SIM_SAMPLED) != 0;
-// the one-launch decoder layer; `samp`: its fused step tail samples the actions (an instantiation of its own, dec_layer_mf.inc)
+  const int kind = tail_of(a);
+  // the lights' tables are written in the element type the launch reads its own tables in (one instantiation per type, not two)
+  if (t && a.tail_mfma && (kind & TK_KIND) == TK_LIGHTS && (a.tl.kv_bf16 != 0) != (p->self_seg.kv_bf16 != 0)) return TBX_ERR_UNSUPPORTED;
+// the one-launch decoder layer, the instantiation of its tail; `samp`: its fused step tail samples the actions (one of its own)
+#define TBX_MF_LAUNCH_T(KERNEL, KV, REL, SAMP, ...) hipLaunchKernelGGL((KERNEL<KV, REL, SAMP, __VA_ARGS__>), grid, dim3(512), 0, hs, arg)
 #define TBX_MF_LAUNCH(KERNEL, KV, REL, GRID, ARG)                                                \
   do {                                                                                          \
-    if (samp) hipLaunchKernelGGL((KERNEL<KV, REL, true>), GRID, dim3(512), 0, hs, ARG);         \
-    else hipLaunchKernelGGL((KERNEL<KV, REL, false>), GRID, dim3(512), 0, hs, ARG);             \
+    const dim3 grid = GRID;                                                                     \
+    const auto& arg = ARG;                                                                      \
+    switch (kind) {                                                                             \
+      case TK_NONE: TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_NONE); break;                    \
+      case TK_NEXT: TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_NEXT); break;                    \
+      case TK_LIGHTS: TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_LIGHTS); break;                \
+      case TK_LIGHTS | TK_SIM: TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_LIGHTS | TK_SIM); break; \
+      case TK_HEADS: TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_HEADS); break;                  \
+      default:                                                                                  \
+        if (samp) TBX_MF_LAUNCH_T(KERNEL, KV, REL, true, TK_HEADS | TK_SIM);                    \
+        else TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_HEADS | TK_SIM);                        \
+    }                                                                                           \
   } while (0)
 #define TBX_MID_LAUNCH(KV, NWV)                                                                                                    \
   do {                                                                                                                            \
@@ -720,6 +745,8 @@ static int dec_launch(const tbx_dec_mid_t* p, const tbx_dec_layer_t* t, void* st
   else
     TBX_MID_LAUNCH(false, 4);
 #undef TBX_MID_LAUNCH
+#undef TBX_MF_LAUNCH
+#undef TBX_MF_LAUNCH_T
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 
@@ -746,6 +773,12 @@ extern "C" int tbx_knarpe_dec_layer_pair(const tbx_dec_layer_t* ta, const tbx_de
   const bool kv16 = ta->mid.self_seg.kv_bf16 != 0;
   if (rel_a != rel_b || kv16 != (tb->mid.self_seg.kv_bf16 != 0) || ta->tail_mfma32 != tb->tail_mfma32) return TBX_ERR_UNSUPPORTED;
   if (ta->tail_mfma32 == 2 && !kv16) return TBX_ERR_UNSUPPORTED;
+  // The pairs a closed-loop step (and the tests) launch, agents' half first: two mid layers, two last layers without a tail, the heads
+  // with the lights' tail - both without or both with their step in the launch. The lights' tables in the launch's element type.
+  const int ka = tail_of(p.m[0]), kb = tail_of(p.m[1]);
+  const bool tails = (ka == TK_HEADS && kb == TK_LIGHTS) || (ka == (TK_HEADS | TK_SIM) && kb == (TK_LIGHTS | TK_SIM));
+  if (!tails && !(ka == kb && (ka == TK_NEXT || ka == TK_NONE))) return TBX_ERR_UNSUPPORTED;
+  if (tails && (p.m[1].tl.kv_bf16 != 0) != kv16) return TBX_ERR_UNSUPPORTED;
   // The halves on disjoint XCDs (workgroup b runs on XCD b % 8): an XCD's L2 then holds ONE half's weight units and K/V rows instead of
   // both - configs[1] (64 + 128 rows): 491.5 -> 499.4 k agent-steps/s with the agents on 3 XCDs (2: 492, 4: 497). Default: the share of
   // XCDs nearest to the halves' share of rows, if both halves then still have a CU per row (32 CUs per XCD); TBX_PAIR_XCD=0: off, n: forced.
@@ -757,7 +790,7 @@ extern "C" int tbx_knarpe_dec_layer_pair(const tbx_dec_layer_t* ta, const tbx_de
     xa = xa < 1 ? 1 : (xa > 7 ? 7 : xa);
     if ((na + xa - 1) / xa > 32 || (nb + 7 - xa) / (8 - xa) > 32) xa = 0;
   }
-  p.xcd_a = 0;
+  p.xcd_a = 0, p.n_rows[0] = na, p.n_rows[1] = nb, p.pad_ = 0;
   unsigned blocks = (unsigned)(na + nb);
   if (xa > 0 && xa < 8) {
     const int sa = (na + xa - 1) / xa, sb = (nb + 7 - xa) / (8 - xa);
@@ -767,18 +800,30 @@ extern "C" int tbx_knarpe_dec_layer_pair(const tbx_dec_layer_t* ta, const tbx_de
   const dim3 grid(blocks);
   hipStream_t hs = (hipStream_t)stream;
   const bool samp = (p.m[0].fused_tail && (p.m[0].sim_parts & tbx_step::SIM_SAMPLED)) || (p.m[1].fused_tail && (p.m[1].sim_parts & tbx_step::SIM_SAMPLED));
+#define TBX_MF_LAUNCH_T(KERNEL, KV, REL, SAMP, ...) hipLaunchKernelGGL((KERNEL<KV, REL, SAMP, __VA_ARGS__>), grid, dim3(512), 0, hs, arg)
+#define TBX_MF_LAUNCH(KERNEL, KV, REL, ARG)                                                                    \
+  do {                                                                                                        \
+    const auto& arg = ARG;                                                                                    \
+    if (ka == TK_NEXT) TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_NEXT, TK_NEXT);                             \
+    else if (ka == TK_NONE) TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_NONE, TK_NONE);                        \
+    else if (ka == TK_HEADS) TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_HEADS, TK_LIGHTS);                    \
+    else if (samp) TBX_MF_LAUNCH_T(KERNEL, KV, REL, true, TK_HEADS | TK_SIM, TK_LIGHTS | TK_SIM);             \
+    else TBX_MF_LAUNCH_T(KERNEL, KV, REL, false, TK_HEADS | TK_SIM, TK_LIGHTS | TK_SIM);                      \
+  } while (0)
   if (ta->tail_mfma32 == 2) {
     MidPair1 q;
     memcpy(&q, &p, sizeof(q));
-    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf1_pair_kernel, true, true, grid, q);
-    else TBX_MF_LAUNCH(dec_layer_mf1_pair_kernel, true, false, grid, q);
+    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf1_pair_kernel, true, true, q);
+    else TBX_MF_LAUNCH(dec_layer_mf1_pair_kernel, true, false, q);
   } else if (kv16) {
-    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, true, true, grid, p);
-    else TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, true, false, grid, p);
+    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, true, true, p);
+    else TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, true, false, p);
   } else {
-    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, false, true, grid, p);
-    else TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, false, false, grid, p);
+    if (rel_a) TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, false, true, p);
+    else TBX_MF_LAUNCH(dec_layer_mf_pair_kernel, false, false, p);
   }
+#undef TBX_MF_LAUNCH
+#undef TBX_MF_LAUNCH_T
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 
