@@ -4,7 +4,8 @@ prototype set. Nothing here computes; the wrappers that launch kernels are in hi
 tests/test_abi_and_host.py compiles the header with gcc and compares every structure's `sizeof` and every field's `offsetof` with the
 classes below. Two headers stand on their own, each with a library and a loader of its own: tbx_hip_grad.h (libtbx_grad.so, `load_grad()`)
 and tbx_hip_sub.h (libtbx_sub.so, `load_sub()`); their mirrors are checked by tests/test_grad_norm_host.py and tests/test_sub_records_host.py.
-tbx_hip_aggr.h (libtbx_aggr.so, `load_aggr()`) is a third of that kind: tests/test_womd_aggr_host.py."""
+tbx_hip_aggr.h (libtbx_aggr.so, `load_aggr()`) is a third of that kind: tests/test_womd_aggr_host.py; tbx_hip_il.h (libtbx_il.so, `load_il()`:
+the imitation terms of the differentiable reward for every criterion / angular type) a fourth: tests/test_il_loss_ref.py."""
 import ctypes as C
 import os
 import re
@@ -15,11 +16,13 @@ _lib = None
 _grad_lib = None
 _sub_lib = None
 _aggr_lib = None
+_il_lib = None
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "csrc" / "libtbx_hip.so"
 GRAD_LIB_PATH = _PKG / "csrc" / "libtbx_grad.so"  # tbx_grad_norms alone (include/tbx_hip_grad.h): libtbx_hip.so's export list is ABI 7's, closed
 SUB_LIB_PATH = _PKG / "csrc" / "libtbx_sub.so"  # tbx_wosac_joint_scenes, tbx_womd_predictions (include/tbx_hip_sub.h), for the same reason
 AGGR_LIB_PATH = _PKG / "csrc" / "libtbx_aggr.so"  # tbx_womd_aggr alone (include/tbx_hip_aggr.h), for the same reason
+IL_LIB_PATH = _PKG / "csrc" / "libtbx_il.so"  # tbx_il_reward_fwd / _bwd, tbx_train_chain_bwd_state (include/tbx_hip_il.h), for the same reason
 HEADER_PATH = _PKG.parent / "include" / "tbx_hip.h"
 
 # ---- constants mirrored from include/tbx_hip.h
@@ -256,6 +259,15 @@ class WomdAggr(C.Structure):
                 + [("aggr_thresh", C.c_float * 3), ("mpa_nms_thresh", C.c_float * 3), ("score_temperature", C.c_float)])
 
 
+class IlReward(C.Structure):
+    """tbx_il_reward_t (include/tbx_hip_il.h: libtbx_il.so, `load_il()`). Filled by hip.il_reward_args."""
+    _fields_ = ([(n, C.c_void_p) for n in ("pred_valid", "pred_pose", "pred_motion", "gt_valid", "gt_pose", "gt_motion", "out_pos", "out_rot",
+                                           "out_spd", "out_sum", "g", "d_pred_pose", "d_pred_spd")] + [("rows", C.c_int64)]
+                + [(n, C.c_int64 * 3) for n in ("valid_stride", "pose_stride", "motion_stride", "out_stride", "g_stride")]
+                + [(n, C.c_int32) for n in ("n_k", "n_ag", "n_step", "n_step_gt", "gt_offset", "crit_pos", "crit_rot", "crit_spd", "angular")]
+                + [(n, C.c_float) for n in ("w_pos", "w_rot", "w_spd")])
+
+
 RULE_COLLIDED, RULE_COLLIDED_WOSAC, RULE_RUN_ROAD_EDGE, RULE_RUN_RED_LIGHT, RULE_PASSIVE = 1, 2, 4, 8, 16
 COLLISION_MAX_AG, COLLISION_LANES = 512, 4  # TBX_COLLISION_* of include/tbx_hip_reward.h: the collision kernels' agent cap / lanes per agent
 METRICS_SLOTS, METRICS_PARTIAL_ROWS = 16, 256  # TBX_METRICS_* of include/tbx_hip_metrics.h: tbx_rollout_metrics' acc vector and workspace rows
@@ -263,6 +275,13 @@ LOSS_PARTIALS = 512  # TBX_LOSS_PARTIALS of include/tbx_hip_loss.h: tbx_loss_sha
 GRAD_CHUNK, GRAD_NORM_2, GRAD_NORM_INF = 8192, 2, 0  # TBX_GRAD_* of include/tbx_hip_grad.h: tbx_grad_norms' chunk size and norm types
 SUB_MAX_OBJECTS = 1024  # TBX_SUB_MAX_OBJECTS of include/tbx_hip_sub.h: most objects per scene on a compacted axis
 AGGR_MAX_K, AGGR_MAX_KEEP, AGGR_MAX_T = 128, 8, 91  # TBX_AGGR_* of include/tbx_hip_aggr.h: tbx_womd_aggr's futures, modes and steps
+# TBX_IL_* / TBX_IL_ANG_* of include/tbx_hip_il.h: the criterion of an imitation term and the angular type of the rotation term, by the
+# names the reference's configuration uses (torch.nn class names; angular_type null = None)
+IL_SMOOTH_L1, IL_MSE, IL_L1, IL_HUBER = 0, 1, 2, 3
+IL_ANG_COSINE, IL_ANG_NONE, IL_ANG_CAST, IL_ANG_VECTOR = 0, 1, 2, 3
+IL_CRITERIA = {"SmoothL1Loss": IL_SMOOTH_L1, "MSELoss": IL_MSE, "L1Loss": IL_L1, "HuberLoss": IL_HUBER}
+IL_ANGULAR = {"cosine": IL_ANG_COSINE, None: IL_ANG_NONE, "cast": IL_ANG_CAST, "vector": IL_ANG_VECTOR}
+IL_SYMBOLS = ("tbx_il_reward_fwd", "tbx_il_reward_bwd", "tbx_train_chain_bwd_state")
 
 _DECL = r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\("
 
@@ -438,4 +457,27 @@ def load_aggr():
     lib.tbx_womd_aggr.restype = C.c_int
     lib.tbx_womd_aggr.argtypes = [C.POINTER(WomdAggr), C.c_void_p]
     _aggr_lib = lib
+    return lib
+
+
+def load_il():
+    """dlopen the in-tree libtbx_il.so (built by the same Makefile) and set the prototypes of its three entry points, tbx_il_reward_fwd,
+    tbx_il_reward_bwd and tbx_train_chain_bwd_state (include/tbx_hip_il.h). No GPU needed. A missing library is an error: there is no
+    fallback path."""
+    global _il_lib
+    if _il_lib is not None:
+        return _il_lib
+    if not IL_LIB_PATH.exists():
+        raise ImportError(f"{IL_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                          "(hipcc --offload-arch=gfx950). There is no fallback path.")
+    lib = C.CDLL(str(IL_LIB_PATH))
+    for name in IL_SYMBOLS:
+        if not hasattr(lib, name):
+            raise ImportError(f"libtbx_il.so does not export {name}")
+        getattr(lib, name).restype = C.c_int
+    lib.tbx_il_reward_fwd.argtypes = [C.POINTER(IlReward), C.c_void_p]
+    lib.tbx_il_reward_bwd.argtypes = [C.POINTER(IlReward), C.c_void_p]
+    lib.tbx_train_chain_bwd_state.argtypes = [C.POINTER(TrainChainArgs), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+    _il_lib = lib
     return lib

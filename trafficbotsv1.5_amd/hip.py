@@ -13,7 +13,7 @@ import torch
 
 from . import abi, hip_base
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
-from .abi import AGGR_LIB_PATH, GRAD_LIB_PATH, HEADER_PATH, LIB_PATH, SUB_LIB_PATH, load, load_aggr, load_grad, load_sub  # noqa: F401
+from .abi import AGGR_LIB_PATH, GRAD_LIB_PATH, HEADER_PATH, IL_LIB_PATH, LIB_PATH, SUB_LIB_PATH, load, load_aggr, load_grad, load_il, load_sub  # noqa: F401
 from .hip_base import *  # noqa: F401,F403  (Seg, stream_ptr, packed_weight / stacked_linear / padded_weight)
 from .hip_base import _attn_args, _check, _cptr, _fill_drop, _ptr  # noqa: F401
 from .hip_chain import *  # noqa: F401,F403  (Chain, group_tile_rows)

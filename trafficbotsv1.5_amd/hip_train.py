@@ -1,7 +1,8 @@
 """ctypes wrappers of the TRAINING entry points of libtbx_hip.so (include/tbx_hip.h): keyed dropout and the one-pass glue ops, the tall
 LINEAR / weight-gradient kernels of the time-batched pass, LayerNorm / PointNet-tail / masked-max-pool forward + backward, the attention
 backward (atomics and inverse-list forms), the per-step state machine (tbx_train_chain_*) and the collision term of the reward
-(include/tbx_hip_reward.h). Re-exported by hip.py."""
+(include/tbx_hip_reward.h), and the imitation terms with the configuration's criteria / angular types (include/tbx_hip_il.h, libtbx_il.so).
+Re-exported by hip.py."""
 import ctypes as C
 import os
 from typing import List, Optional, Sequence
@@ -9,7 +10,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .abi import *  # noqa: F401,F403  (constants, structures, load, declared_symbols: the C-ABI mirror)
-from .abi import load  # noqa: F401
+from .abi import load, load_il  # noqa: F401
 from .hip_base import Seg, _attn_args, _check, _cptr, _derived, _name, _ptr, drop_mix, drop_rate, drop_stream_key, drop_struct, packed_weight, stream_ptr
 
 
@@ -365,3 +366,71 @@ def collision_reward_bwd(pose: torch.Tensor, valid: torch.Tensor, ag_size: torch
     _check(load().tbx_collision_reward_bwd(*_collision_log_args(pose, valid, ag_size, n_k), int(bool(reduce_with_max)), _ptr(g), g.stride(0),
                                            g.stride(2), g.stride(1), _ptr(arg, torch.int32), _ptr(d_pose), stream_ptr()), "tbx_collision_reward_bwd")
     return d_pose
+
+
+def il_reward_args(pred_valid: torch.Tensor, pred_pose: torch.Tensor, pred_motion: torch.Tensor, gt_valid: torch.Tensor, gt_pose: torch.Tensor,
+                   gt_motion: torch.Tensor, codes: Sequence[int], weights: Sequence[float], gt_offset: int, n_k: int = 1) -> IlReward:
+    """tbx_il_reward_t for the views pred_valid [rows, T, A] u8 / bool, pred_pose / pred_motion [rows, T, A, 3] f32 of any strides (the
+    triples contiguous) - a permuted agent-major log is read where it lies - and the dense ground truth [rows / n_k, A, Tg(, 3)].
+    codes = (crit_pos, crit_rot, crit_spd, angular), weights = (w_pos, w_rot, w_spd); slot t is compared with ground-truth index t + gt_offset."""
+    rows, T, A, three = pred_pose.shape
+    assert three == 3 and pred_pose.stride(3) == 1 and pred_motion.stride(3) == 1 and tuple(pred_motion.shape) == (rows, T, A, 3)
+    assert tuple(pred_valid.shape) == (rows, T, A) and pred_valid.dtype in (torch.uint8, torch.bool)
+    assert pred_pose.dtype == pred_motion.dtype == gt_pose.dtype == gt_motion.dtype == torch.float32 and gt_valid.dtype in (torch.uint8, torch.bool)
+    assert rows % n_k == 0 and gt_valid.dim() == 3 and tuple(gt_valid.shape[:2]) == (rows // n_k, A)
+    Tg = gt_valid.shape[2]
+    assert tuple(gt_pose.shape) == tuple(gt_motion.shape) == (rows // n_k, A, Tg, 3)
+    assert gt_valid.is_contiguous() and gt_pose.is_contiguous() and gt_motion.is_contiguous()
+    a = IlReward()
+    a.pred_valid, a.pred_pose, a.pred_motion = _ptr(pred_valid), _ptr(pred_pose), _ptr(pred_motion)
+    a.gt_valid, a.gt_pose, a.gt_motion = _ptr(gt_valid), _ptr(gt_pose), _ptr(gt_motion)
+    a.rows, a.n_k, a.n_ag, a.n_step, a.n_step_gt, a.gt_offset = rows, int(n_k), A, T, Tg, int(gt_offset)
+    for name, t in (("valid_stride", pred_valid), ("pose_stride", pred_pose), ("motion_stride", pred_motion)):
+        setattr(a, name, (C.c_int64 * 3)(t.stride(0), t.stride(1), t.stride(2)))
+    a.crit_pos, a.crit_rot, a.crit_spd, a.angular = (int(c) for c in codes)
+    a.w_pos, a.w_rot, a.w_spd = (float(w) for w in weights)
+    return a
+
+
+def il_reward_fwd(pred_valid, pred_pose, pred_motion, gt_valid, gt_pose, gt_motion, codes, weights, gt_offset: int, n_k: int = 1,
+                  out4: Optional[torch.Tensor] = None, out_sum: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tbx_il_reward_fwd on [rows, T, A(, 3)] views (il_reward_args). out4: a [rows, T, A, 4] f32 view of any strides (the four columns
+    contiguous) that receives r_pos, r_rot, r_spd and their sum; else only the sum, into the [rows, T, A] view out_sum (default: a new
+    tensor). Returns the tensor written."""
+    a = il_reward_args(pred_valid, pred_pose, pred_motion, gt_valid, gt_pose, gt_motion, codes, weights, gt_offset, n_k)
+    rows, T, A = pred_valid.shape
+    if out4 is not None:
+        assert tuple(out4.shape) == (rows, T, A, 4) and out4.dtype == torch.float32 and out4.stride(3) == 1 and out4.device == pred_pose.device
+        base, out = out4.data_ptr(), out4
+        a.out_pos, a.out_rot, a.out_spd, a.out_sum = base, base + 4, base + 8, base + 12
+    else:
+        out = torch.empty(rows, T, A, dtype=torch.float32, device=pred_pose.device) if out_sum is None else out_sum
+        assert tuple(out.shape) == (rows, T, A) and out.dtype == torch.float32 and out.device == pred_pose.device
+        a.out_sum = _ptr(out)
+    a.out_stride = (C.c_int64 * 3)(out.stride(0), out.stride(1), out.stride(2))
+    _check(load_il().tbx_il_reward_fwd(C.byref(a), stream_ptr()), "tbx_il_reward_fwd")
+    return out
+
+
+def il_reward_bwd(pred_valid, pred_pose, pred_motion, gt_valid, gt_pose, gt_motion, codes, weights, gt_offset: int, g: torch.Tensor, n_k: int = 1):
+    """tbx_il_reward_bwd -> (d_pred_pose [rows, T, A, 3], d_pred_spd [rows, T, A]), dense, from g = dL/d(sum), a [rows, T, A] view of any strides."""
+    a = il_reward_args(pred_valid, pred_pose, pred_motion, gt_valid, gt_pose, gt_motion, codes, weights, gt_offset, n_k)
+    rows, T, A = pred_valid.shape
+    assert tuple(g.shape) == (rows, T, A) and g.dtype == torch.float32 and g.device == pred_pose.device
+    d_pose = torch.empty(rows, T, A, 3, dtype=torch.float32, device=pred_pose.device)
+    d_spd = torch.empty(rows, T, A, dtype=torch.float32, device=pred_pose.device)
+    a.g, a.g_stride = _ptr(g), (C.c_int64 * 3)(g.stride(0), g.stride(1), g.stride(2))
+    a.d_pred_pose, a.d_pred_spd = _ptr(d_pose), _ptr(d_spd)
+    _check(load_il().tbx_il_reward_bwd(C.byref(a), stream_ptr()), "tbx_il_reward_bwd")
+    return d_pose, d_spd
+
+
+def train_chain_bwd_state(args: TrainChainArgs, mean: torch.Tensor, stride_n: int, stride_t: int, d_reward: torch.Tensor,
+                          d_pred_pose: Optional[torch.Tensor], d_pred_spd: Optional[torch.Tensor], d_mean: torch.Tensor):
+    """tbx_train_chain_bwd_state (libtbx_il.so): the reverse walk with d_pred_pose [n,T,A,3] / d_pred_spd [n,T,A] (dense; None: absent) added
+    to the predictions' adjoint."""
+    assert d_pred_pose is None or d_pred_pose.is_contiguous()
+    assert d_pred_spd is None or d_pred_spd.is_contiguous()
+    _check(load_il().tbx_train_chain_bwd_state(C.byref(args), _ptr(mean, torch.float32), stride_n, stride_t, _ptr(d_reward, torch.float32),
+                                               _cptr(d_pred_pose, torch.float32), _cptr(d_pred_spd, torch.float32), _ptr(d_mean, torch.float32),
+                                               stream_ptr()), "tbx_train_chain_bwd_state")

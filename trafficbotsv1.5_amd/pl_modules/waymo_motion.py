@@ -89,15 +89,12 @@ class WaymoMotion(LightningModule):
                                       "(the default is the deterministic action)")
         self.save_hyperparameters()  # self.hparams.<constructor argument>, as in the reference (waymo_motion.py:66)
         # tbx_sim_step / tbx_train_chain log the DEFAULT imitation terms of DifferentiableReward (rewards.py:35-74: SmoothL1 position /
-        # speed terms, a cosine SmoothL1 rotation term); anything else would yield a plausible but wrong RolloutBuffer. The collision
-        # approximation (w_collision > 0, rewards.py:76-154) is a launch of its own over the finished pose log (tbx_collision_reward_*).
+        # speed terms, a cosine rotation term). Any other criterion / angular type of the configuration (DifferentiableReward checks the
+        # names) is a launch of its own over the finished log (tbx_il_reward_*), as the collision approximation is (w_collision > 0,
+        # rewards.py:76-154: tbx_collision_reward_*). Without the imitation terms the state machine's reward would be plausible but wrong.
         rc = to_attr(dict(differentiable_reward))
         if not rc.get("is_enabled", True) or not rc.get("use_il_loss", True):
             raise NotImplementedError("differentiable_reward: only is_enabled with use_il_loss is implemented in the HIP state machine")
-        for term, ang in (("l_pos", None), ("l_rot", "cosine"), ("l_spd", None)):
-            t = rc[term]
-            if t.get("criterion", "SmoothL1Loss") != "SmoothL1Loss" or (ang is not None and t.get("angular_type", ang) != ang):
-                raise NotImplementedError(f"differentiable_reward.{term}: only SmoothL1Loss" + (" with angular_type=cosine" if ang else "") + " is implemented")
         pp = [(k, SceneCentricPreProcessing(time_step_current=time_step_current, data_size=data_size, **_strip_target(v)))
               for k, v in pre_processing.items()]
         kwargs = {"time_step_gt": time_step_gt}
@@ -224,7 +221,8 @@ class WaymoMotion(LightningModule):
             eng = self.begin_rollout(ag_tokens, mp_tokens, tl_tokens, tl_state_gt, teacher_forcing, rule_checker, step_end,
                                      deterministic_action=deterministic_action)
             eng.run(step_end, use_graph=use_graph)
-            return eng.buffer(self.hp.time_step_current, rule_checker=rule_checker, collision=self._collision_args(ag_tokens, rule_checker))
+            return eng.buffer(self.hp.time_step_current, rule_checker=rule_checker, collision=self._collision_args(ag_tokens, rule_checker),
+                              imitation=self.diffbar_reward.il_config)
         # ---- the reference's loop, statement by statement (waymo_motion.py:218-311)
         teacher_forcing.init(ag_valid=ag_tokens["gt_valid"], ag_pose=ag_tokens["gt_pose"], ag_motion=ag_tokens["gt_motion"],
                              tl_state=tl_state_gt, current_epoch=self.current_epoch)
@@ -243,9 +241,13 @@ class WaymoMotion(LightningModule):
             violation = rule_checker.check(pred_dict["pred_valid"], pred_dict["pred_pose"], pred_dict["pred_motion"], dyn.tl_state)
             _gt_valid = ag_tokens["gt_valid"][:, :, _step] if _step < Tg else None
             # reward and light NLL as tbx_sim_step logged them for this step (the expressions of self.diffbar_reward.get and of
-            # -pred_tl_state_dist.log_prob: the engine's own loop hands out the same log)
+            # -pred_tl_state_dist.log_prob: the engine's own loop hands out the same log); imitation terms with other criteria than
+            # the step's own: self.diffbar_reward's, on this step's prediction (the values add_imitation_terms gives the engine's loop)
             S, slot = self._engine.S, _step - 1
             r = S["out_reward"][:, :, slot]
+            if self.diffbar_reward.il_config is not None and _step < Tg:
+                r = self.diffbar_reward.imitation(pred_dict["pred_valid"], pred_dict["pred_pose"], pred_dict["pred_motion"], _gt_valid,
+                                                  ag_tokens["gt_pose"][:, :, _step], ag_tokens["gt_motion"][:, :, _step])
             reward = {"diffbar_reward_valid": S["out_reward_valid"][:, :, slot].bool(), "diffbar_reward": r[..., 3],
                       "r_imitation_pos": r[..., 0], "r_imitation_rot": r[..., 1], "r_imitation_spd": r[..., 2],
                       "r_traffic_rule_approx": torch.zeros_like(r[..., 0])}

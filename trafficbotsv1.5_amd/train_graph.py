@@ -476,9 +476,12 @@ def training_rollout(wm, b, mp, tl_tokens, z, z_valid, tf_mask: Tensor, step_end
         if step < Tg:  # rewards.py:58-74
             g_valid, g_pose, g_motion = gt_valid[:, :, step], gt_pose[:, :, step], gt_motion[:, :, step]
             r_valid = pred_valid & g_valid
-            e_pos = F.smooth_l1_loss(g_pose[..., :2], pred_pose[..., :2], reduction="none").sum(-1)
-            e_rot = 0.5 * (1 - torch.cos(g_pose[..., 2] - pred_pose[..., 2]))
-            e_spd = F.smooth_l1_loss(g_motion[..., 0], pred_motion[..., 0], reduction="none")
+            if il_config(wm) is None:
+                e_pos = F.smooth_l1_loss(g_pose[..., :2], pred_pose[..., :2], reduction="none").sum(-1)
+                e_rot = 0.5 * (1 - torch.cos(g_pose[..., 2] - pred_pose[..., 2]))
+                e_spd = F.smooth_l1_loss(g_motion[..., 0], pred_motion[..., 0], reduction="none")
+            else:  # the configuration's criteria / angular type as torch expressions (the checked reference of the fused chain's kernels)
+                e_pos, e_rot, e_spd = wm.diffbar_reward.torch_errors(g_pose, g_motion, pred_pose, pred_motion)
             rew = ((-rc.l_pos.weight * e_pos).masked_fill(~r_valid, 0) + (-rc.l_rot.weight * e_rot).masked_fill(~r_valid, 0)
                    + (-rc.l_spd.weight * e_spd).masked_fill(~r_valid, 0))
             dis = out_now & ~g_valid

@@ -642,6 +642,12 @@ class TrainChain:
         a = hip.TrainChainArgs()
         a.n_batch, a.n_ag, a.n_step, a.n_step_gt, a.n_node, a.window = n, A, T, Tg, N, W
         a.dt, a.w_pos, a.w_rot, a.w_spd = float(dyn.dt), float(rc.l_pos.weight), float(rc.l_rot.weight), float(rc.l_spd.weight)
+        # imitation terms with other criteria / angular type than the chain's own (SmoothL1, cosine): None | (codes, weights). The chain
+        # then runs with zero weights - it differentiates no imitation term of its own, its reward_valid and all its state logic stand -
+        # and TrainChainFn computes the terms from the finished pred_* log (tbx_il_reward_fwd / _bwd, tbx_train_chain_bwd_state)
+        self.il = il_config(wm)
+        if self.il is not None:
+            a.w_pos = a.w_rot = a.w_spd = 0.0
         for name, v in self.t.items():
             setattr(a, name, v.data_ptr())
         self.args = a
@@ -722,7 +728,14 @@ class TrainChain:
 
 class TrainChainFn(torch.autograd.Function):
     """reward [n,T,A] of the whole rollout from the batched action means [n,T,A,2] (tbx_train_chain_fwd over all steps from the
-    initial state); backward = tbx_train_chain_bwd (reverse walk over the steps)."""
+    initial state); backward = tbx_train_chain_bwd (reverse walk over the steps). With chain.il set the imitation terms are
+    tbx_il_reward_fwd's over the finished prediction log, and the backward is tbx_il_reward_bwd followed by the reverse walk with the
+    adjoints of the prediction it produced (tbx_train_chain_bwd_state)."""
+
+    @staticmethod
+    def _il_views(chain):
+        t = chain.t
+        return t["pred_valid"], t["pred_pose"], t["pred_motion"], t["gt_valid"], t["gt_pose"], t["gt_motion"]
 
     @staticmethod
     def forward(ctx, mean, chain):
@@ -730,14 +743,18 @@ class TrainChainFn(torch.autograd.Function):
         chain.reset()
         hip.train_chain_fwd(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, 0, chain.T)
         ctx.chain = chain
+        if chain.il is not None:  # (the chain's own reward is 0 everywhere: its weights are)
+            reward = hip.il_reward_fwd(*TrainChainFn._il_views(chain), *chain.il, gt_offset=1)
+        else:
+            reward = chain.t["reward"]
         if chain.collision is None:
             ctx.save_for_backward(mean)
-            return chain.t["reward"].clone()
+            return reward.clone() if chain.il is None else reward
         w, reduce_max, ag_size = chain.collision
         c, arg = hip.collision_reward_fwd(chain.t["pred_pose"], chain.t["pred_valid"], ag_size, reduce_max)
         chain.rule_apx = _weighted_collision(c, chain.t["pred_valid"], w)
         ctx.save_for_backward(mean, *(() if arg is None else (arg,)))
-        return chain.t["reward"] + chain.rule_apx
+        return reward + chain.rule_apx
 
     @staticmethod
     def backward(ctx, d_reward):
@@ -745,14 +762,28 @@ class TrainChainFn(torch.autograd.Function):
         chain = ctx.chain
         d_mean = torch.empty_like(mean)
         d_reward = d_reward.contiguous()
-        if chain.collision is None:
+        d_pose = d_spd = None
+        if chain.il is not None:
+            d_pose, d_spd = hip.il_reward_bwd(*TrainChainFn._il_views(chain), *chain.il, gt_offset=1, g=d_reward)
+        if chain.collision is not None:
+            w, reduce_max, ag_size = chain.collision
+            g = _weighted_collision(d_reward, chain.t["pred_valid"], w)  # dL/dc
+            d_col = hip.collision_reward_bwd(chain.t["pred_pose"], chain.t["pred_valid"], ag_size, reduce_max, g, arg[0] if arg else None)
+            d_pose = d_col if d_pose is None else d_pose.add_(d_col)
+        if chain.il is not None:
+            hip.train_chain_bwd_state(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, d_reward, d_pose, d_spd, d_mean)
+        elif chain.collision is None:
             hip.train_chain_bwd(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, d_reward, d_mean)
-            return d_mean, None
-        w, reduce_max, ag_size = chain.collision
-        g = _weighted_collision(d_reward, chain.t["pred_valid"], w)  # dL/dc
-        d_pose = hip.collision_reward_bwd(chain.t["pred_pose"], chain.t["pred_valid"], ag_size, reduce_max, g, arg[0] if arg else None)
-        hip.train_chain_bwd_pose(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, d_reward, d_pose, d_mean)
+        else:
+            hip.train_chain_bwd_pose(chain.args, mean, chain.T * chain.A * 2, chain.A * 2, d_reward, d_pose, d_mean)
         return d_mean, None
+
+
+def il_config(wm):
+    """DifferentiableReward.il_config of a module: (codes, weights) when its imitation terms are not the chain's own, else None - then
+    nothing of libtbx_il.so is launched."""
+    r = getattr(wm, "diffbar_reward", None)
+    return None if r is None or not r.is_enabled else r.il_config
 
 
 def collision_config(wm, b):

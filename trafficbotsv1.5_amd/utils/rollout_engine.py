@@ -62,6 +62,18 @@ def add_collision_term(reward: Dict[str, Tensor], pred_valid: Tensor, pred_pose:
     reward["diffbar_reward_valid"] = valid
 
 
+def add_imitation_terms(out_reward: Tensor, pred_valid: Tensor, pred_pose: Tensor, pred_motion: Tensor, gt_valid: Tensor, gt_pose: Tensor,
+                        gt_motion: Tensor, codes, weights) -> None:
+    """The imitation terms of a differentiable reward whose criteria / angular type are not the ones written into tbx_sim_step
+    (DifferentiableReward.il_config), over a finished log, in place: ONE tbx_il_reward_fwd launch over the agent-major log pred_valid
+    [n, A, T] (u8 / bool), pred_pose / pred_motion [n, A, T, 3] - read where it lies - against the ground truth [n, A, Tg(, 3)] (slot t
+    holds step t + 1) replaces the four planes r_pos, r_rot, r_spd, sum of out_reward [n, A, T, 4]. The mask (pred & gt valid, the
+    prediction's validity past the ground truth) does not depend on the criteria: out_reward_valid stays."""
+    u8 = lambda t: t if t.dtype in (torch.uint8, torch.bool) else t.to(torch.uint8)
+    hip.il_reward_fwd(u8(pred_valid).permute(0, 2, 1), pred_pose.permute(0, 2, 1, 3), pred_motion.permute(0, 2, 1, 3), u8(gt_valid).contiguous(),
+                      gt_pose.float().contiguous(), gt_motion.float().contiguous(), codes, weights, gt_offset=1, out4=out_reward.permute(0, 2, 1, 3))
+
+
 def lights_per_scene(tl_tokens: Dict[str, Tensor], k: int) -> Dict[str, Tensor]:
     """Per-scene view of traffic-light tokens that were expanded per rollout (`encode_scene(n_rollout=k)`: every per-light
     tensor repeated k times along the batch, map targets indexed per scene through mp_batch_div = k): entry 0 of every group
@@ -735,12 +747,14 @@ class RolloutEngine:
             lp = lp.unsqueeze(-1)
         return lp * valid_u8.to(lp.dtype)
 
-    def buffer(self, step_current: int = 10, rule_checker=None, collision=None) -> RolloutBuffer:
+    def buffer(self, step_current: int = 10, rule_checker=None, collision=None, imitation=None) -> RolloutBuffer:
         """The rollout log as the reference's RolloutBuffer. With a TrafficRuleChecker, the five metric-only rule checks
         (collided, collided_wosac, run_road_edge, run_red_light, passive: waymo_motion.py:250 in the reference's loop) are
         evaluated here for all steps at once from the device-resident log (tbx_rule_check over n x T frames).
         collision = (w_collision, reduce_with_max, ag_size [n, A, 3]) of a reward with w_collision > 0: the term that couples the agents
-        is computed here from the finished pose log, one launch (add_collision_term); None: no launch, the term's log is zeros."""
+        is computed here from the finished pose log, one launch (add_collision_term); None: no launch, the term's log is zeros.
+        imitation = (codes, weights) of a reward whose imitation terms are not tbx_sim_step's own (DifferentiableReward.il_config): the
+        four reward planes are replaced from the finished log, one launch (add_imitation_terms), before the collision term; None: no launch."""
         S, buf = self.S, RolloutBuffer(self.T, step_current)
         if getattr(self, "tl_share_ok", None) is not None:
             ok, self.tl_share_ok = self.tl_share_ok, None
@@ -769,6 +783,9 @@ class RolloutEngine:
             buf.vis_dict["action_noise"] = S["out_act_noise"]  # the eps every sampled action was drawn with
         # what the reference's loop adds per step besides the prediction (waymo_motion.py:250-300)
         r = S["out_reward"]
+        if imitation is not None:
+            r = r if self.reused else r.clone()  # (a cached engine's buffer already owns a copy; the engine's own log keeps what the step logged)
+            add_imitation_terms(r, S["out_valid"], S["out_pose"], S["out_motion"], S["gt_valid"], S["gt_pose"], S["gt_motion"], *imitation)
         buf.diffbar_reward = {"diffbar_reward_valid": b8(S["out_reward_valid"]), "diffbar_reward": r[..., 3],
                               "r_imitation_pos": r[..., 0], "r_imitation_rot": r[..., 1], "r_imitation_spd": r[..., 2],
                               "r_traffic_rule_approx": torch.zeros_like(r[..., 0])}
