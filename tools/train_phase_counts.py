@@ -29,7 +29,7 @@ def wrap(name, fn):
         marks.append((name + ":end", ev()))
         return r
     return f
-for name in ("map_encoder", "tl_pre_compute", "latent_posterior", "navi_predictor", "training_rollout", "policy_step", "tl_encoder", "training_loss"):
+for name in ("map_encoder", "tl_pre_compute", "latent_dist", "navi_predictor", "training_rollout", "policy_step", "tl_encoder", "training_loss"):
     setattr(TG, name, wrap(name, getattr(TG, name)))
 from torch.profiler import profile, ProfilerActivity
 with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:

@@ -8,9 +8,10 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from torch.distributions import Independent, Normal, kl_divergence
+from torch.distributions import Independent, Normal, OneHotCategoricalStraightThrough, kl_divergence
 
 from ... import abi
+from ..modules.distributions import one_hot_categorical
 
 # the criteria of an imitation term by the reference's names (torch.nn classes with reduction="none") as torch expressions of
 # (input, target): what the torch state machine of the training step differentiates, and the CPU path of the classes below.
@@ -70,18 +71,30 @@ class AngularError:
         return e.view(preds.shape)
 
 
+def detached(d: Independent) -> Independent:
+    """A latent distribution (Independent over Normal or over the one-hot categorical) without its graph (loss.py:59-66): the Normal from
+    its detached loc / scale, the categorical from its detached probabilities."""
+    b = d.base_dist
+    if isinstance(b, Normal):
+        return Independent(Normal(b.loc.detach(), b.scale.detach(), validate_args=False), 1, validate_args=False)
+    return one_hot_categorical(probs=b.probs.detach())
+
+
 class BalancedKL:
-    """Dreamer-v2 KL balancing (loss.py:39-77) for the diagonal-Gaussian latents of the default configuration."""
+    """Dreamer-v2 KL balancing (loss.py:39-77) of two latent distributions of one family: diagonal Gaussians (latent_encoder std_gaus /
+    diag_gaus) or multi-categoricals (std_cat / cat). A pair of different families: ValueError."""
 
     def __init__(self, kl_balance_scale: float, kl_free_nats: float) -> None:
         self.alpha, self.free_nats = kl_balance_scale, kl_free_nats
 
     def compute(self, posterior: Independent, prior: Independent) -> Tensor:
-        if not isinstance(posterior.base_dist, Normal):
-            raise NotImplementedError("BalancedKL: diagonal-Gaussian latents (latent_encoder diag_gaus / std_gaus)")
-        det = lambda d: Independent(Normal(d.base_dist.loc.detach(), d.base_dist.scale.detach(), validate_args=False), 1, validate_args=False)
+        fam = lambda d: Normal if isinstance(d.base_dist, Normal) else (
+            OneHotCategoricalStraightThrough if isinstance(d.base_dist, OneHotCategoricalStraightThrough) else None)
+        if fam(posterior) is None or fam(posterior) is not fam(prior):
+            raise ValueError(f"BalancedKL: posterior {type(posterior.base_dist).__name__} and prior {type(prior.base_dist).__name__} "
+                             f"must both be Normal or both be OneHotCategoricalStraightThrough")
         if self.alpha > 0:
-            e0, e1 = kl_divergence(det(posterior), prior), kl_divergence(posterior, det(prior))
+            e0, e1 = kl_divergence(detached(posterior), prior), kl_divergence(posterior, detached(prior))
             if self.free_nats > 0:
                 e0, e1 = torch.clamp(e0, min=self.free_nats), torch.clamp(e1, min=self.free_nats)
             return e0 + self.alpha * e1

@@ -405,7 +405,11 @@ class GraphedTrainStep:
         dev = next(wm.model.parameters()).device
         self.static = self._pre(example_batch)  # static input buffers: the re-keyed (sc/*, gt/*, ref/*) batch
         n, A = example_batch["agent/valid"].shape[:2]
-        self.noise = torch.zeros(n, A, wm.model.latent_encoder.out_dim, device=dev)
+        le = wm.model.latent_encoder
+        # normal noise [n, A, latent] of a Gaussian latent; uniform noise in (0, 1) of the logits' shape of a categorical one
+        self._uniform_noise = le.categorical
+        self.noise = (torch.full((n, A, le.latent_dist_post.n_cat, le.latent_dist_post.n_class), 0.5, device=dev) if le.categorical
+                      else torch.zeros(n, A, le.out_dim, device=dev))
         self.use_prior = torch.zeros((), dtype=torch.bool, device=dev)
         self._noise_pin, self._noise_turn = None, 0  # pinned staging of the host-drawn noise (_refill)
         wm.attn_dropout_seed = self.drop_seed = torch.zeros(1, dtype=torch.int64, device=dev)  # static: the graph reads it
@@ -521,7 +525,10 @@ class GraphedTrainStep:
         buf, ev = self._noise_pin[self._noise_turn]
         self._noise_turn ^= 1
         ev.synchronize()  # (the copy that last read this buffer has run; a fresh event is complete)
-        torch.randn(self.noise.shape, out=buf)
+        if self._uniform_noise:
+            torch.rand(self.noise.shape, out=buf).clamp_(min=torch.finfo(buf.dtype).tiny)
+        else:
+            torch.randn(self.noise.shape, out=buf)
         self.noise.copy_(buf, non_blocking=True)
         ev.record()
         self.use_prior.fill_(bool(torch.rand(1) < self.wm.hp.p_training_rollout_prior))

@@ -30,13 +30,14 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from torch.distributions import Categorical, Independent, Normal, kl_divergence
+from torch.distributions import Categorical
 
 from . import hip, hip_base
 from . import train_state as ST
 from . import train_state as state  # noqa: F401  (tests switch paths / classes through train_graph.state.X)
 from .hip import Seg
-from .models.modules.distributions import DestCategorical, DiagGaussian
+from .models.metrics.loss import BalancedKL
+from .models.modules.distributions import DestCategorical, DiagGaussian, MultiCategorical
 from .train_ops import *  # noqa: F401,F403  (autograd Functions + linear / layer_norm / residual / mlp / pointnet / attention helpers)
 from .train_ops import _attn_residual, _drop, _drop_args, _glue_ok, _pointnet_fused_ok  # noqa: F401
 from .utils.teacher_forcing import threshold_resets
@@ -310,18 +311,53 @@ def policy_step(model, hist, ag_attr6, ag_type, ag_valid, ag_pose, z, z_valid, d
     return mean.view(n, A, 2), logits.view(n, L, -1)
 
 
-def latent_posterior(le, b, mp, tl_tokens, training: bool) -> DiagGaussian:
+def dist_head(de, feat: Tensor, valid: Tensor, ag_type: Tensor):
+    """models/latent_encoder.py `DistEncoder` on the agent features [n * A, 128], differentiable (latent_encoder.py:216-253 of the
+    reference): the MLP outputs zeroed on ~valid rows, or with branch_type summed over the three types under ~(ag_type & valid)."""
+    n, A = valid.shape
+
+    def head(mlps) -> Tensor:
+        if not de.branch_type:
+            return mlp(mlps, feat).view(n, A, -1).masked_fill(~valid.unsqueeze(-1), 0.0)
+        mask_type = ~(ag_type & valid.unsqueeze(-1)).reshape(n * A, 3)
+        out = 0
+        for i, m in enumerate(mlps):
+            out = out + mlp(m, feat).masked_fill(mask_type[:, i:i + 1], 0.0)
+        return out.view(n, A, -1)
+
+    if de.dist_type == "cat":
+        return MultiCategorical(head(de.mlp_logits).view(n, A, de.n_cat, de.n_class), valid=valid)
+    assert de.dist_type == "diag_gaus", de.dist_type
+    mean = head(de.mlp_mean)
+    if de.log_std is None:
+        log_std = head(de.mlp_log_std)
+    else:
+        log_std = de.masked_log_std(valid, ag_type) if de.branch_type else de.log_std
+    return DiagGaussian(mean, log_std, valid=valid)
+
+
+def latent_dist(le, b, mp, tl_tokens, training: bool, posterior: bool = True):
+    """The latent distribution of one side with autograd: the posterior from the ground-truth episode (gt/*) through the *_post modules,
+    a learned prior from the history (sc/*) through the *_prior modules (waymo_motion.py:326-347). Both are down-sampled and
+    left-padded into the encoders' window. The prior's `valid` is the history's any() AFTER the down-sampling
+    (latent_encoder.py:97-102,122 of the reference); the posterior's stays the full-rate any() it has been."""
     r = le.temporal_down_sample_rate
-    v, m, p, s = b["gt/ag_valid"][:, :, ::r], b["gt/ag_motion"][:, :, ::r], b["gt/ag_pose"][:, :, ::r], b["gt/tl_state"][:, :, ::r]
-    te, ae = le.tl_encoder_post, le.ag_encoder_post
-    n, A, _ = v.shape
+    src = "gt" if posterior else "sc"
+    v, m, p, s = b[src + "/ag_valid"][:, :, ::r], b[src + "/ag_motion"][:, :, ::r], b[src + "/ag_pose"][:, :, ::r], b[src + "/tl_state"][:, :, ::r]
+    te, ae = (le.tl_encoder_post, le.ag_encoder_post) if posterior else (le.tl_encoder_prior, le.ag_encoder_prior)
+    de = le.latent_dist_post if posterior else le.latent_dist_prior
     tl_feat = tl_encoder(te, te.states_to_hist(s, te.temp_window_size), tl_tokens, training)
     hv, hp, hm = ae.pad_hist(v, p, m, ae.temp_window_size)
     feat, _ = agent_encoder(ae, hv, hp, hm, b["sc/ag_attr"].float().contiguous(), mp, tl_tokens["tl_token_invalid_u8"],
                             tl_tokens["tl_token_pose"], tl_feat, training)
-    valid = b["gt/ag_valid"].any(-1)
-    mean = mlp(le.latent_dist_post.mlp_mean, feat).view(n, A, -1).masked_fill(~valid.unsqueeze(-1), 0.0)
-    return DiagGaussian(mean, le.latent_dist_post.log_std, valid=valid)
+    valid = b["gt/ag_valid"].any(-1) if posterior else v.any(-1)
+    return dist_head(de, feat, valid, b["ref/ag_type"])
+
+
+def balanced_kl(cfg, post, prior) -> Tensor:
+    """metrics/loss.py:39-77 on two latent distributions of one family -> [n, A]: max(KL(sg(post) || prior), free nats) +
+    kl_balance_scale * max(KL(post || sg(prior)), free nats)."""
+    return BalancedKL(cfg.kl_balance_scale, cfg.kl_free_nats).compute(post.distribution, prior.distribution)
 
 
 def navi_predictor(npd, b, mp, training: bool) -> DestCategorical:
@@ -734,13 +770,8 @@ def _training_loss_shaped(cfg, ro, navi_pred, navi_gt, post, prior, counts, ag_r
     cnt = lambda m: m.sum().clamp(min=1)
     total, n_rv, any_valid, w_agent = shaped_reward(cfg, ro["pred_valid"], ro["tf"], ro["reward"], ro["reward_valid"], ag_role, pick)
     weighted = (lambda e: e) if w_agent is None else (lambda e: e * w_agent)
-    P, Q = post.distribution, prior.distribution
-    dP = Independent(Normal(P.base_dist.loc.detach(), P.base_dist.scale.detach(), validate_args=False), 1, validate_args=False)
-    dQ = Independent(Normal(Q.base_dist.loc.detach(), Q.base_dist.scale.detach(), validate_args=False), 1, validate_args=False)
-    e0 = torch.clamp(kl_divergence(dP, Q), min=cfg.kl_free_nats)
-    e1 = torch.clamp(kl_divergence(P, dQ), min=cfg.kl_free_nats)
     kv = (post.valid if cfg.kl_for_unseen_agent else prior.valid) & any_valid
-    vae_kl = cfg.w_vae_kl * weighted(e0 + cfg.kl_balance_scale * e1).masked_fill(~kv, 0).sum() / cnt(kv)
+    vae_kl = cfg.w_vae_kl * weighted(balanced_kl(cfg, post, prior)).masked_fill(~kv, 0).sum() / cnt(kv)
     reward = cfg.w_diffbar_reward * total / n_rv.clamp(min=1)
     nv = navi_pred.valid & any_valid
     navi = cfg.w_navi * weighted(-navi_pred.log_prob(navi_gt)).masked_fill(~nv, 0).sum() / cnt(nv)
@@ -769,13 +800,8 @@ def training_loss(cfg, ro, navi_pred: DestCategorical, navi_gt, post: DiagGaussi
     if not cfg.loss_for_teacher_forcing:
         lv &= ~ro["tf"]
     any_valid = lv.any(-1)
-    P, Q = post.distribution, prior.distribution
-    dP = Independent(Normal(P.base_dist.loc.detach(), P.base_dist.scale.detach(), validate_args=False), 1, validate_args=False)
-    dQ = Independent(Normal(Q.base_dist.loc.detach(), Q.base_dist.scale.detach(), validate_args=False), 1, validate_args=False)
-    e0 = torch.clamp(kl_divergence(dP, Q), min=cfg.kl_free_nats)
-    e1 = torch.clamp(kl_divergence(P, dQ), min=cfg.kl_free_nats)
     kv = (post.valid if cfg.kl_for_unseen_agent else prior.valid) & any_valid
-    vae_kl = cfg.w_vae_kl * (e0 + cfg.kl_balance_scale * e1).masked_fill(~kv, 0).sum() / cnt(kv)
+    vae_kl = cfg.w_vae_kl * balanced_kl(cfg, post, prior).masked_fill(~kv, 0).sum() / cnt(kv)
     rv = lv & ro["reward_valid"]
     reward = cfg.w_diffbar_reward * ro["reward"].masked_fill(~rv, 0).sum() / cnt(rv)
     nv = navi_pred.valid & any_valid
@@ -846,22 +872,37 @@ def _training_step(wm, raw_batch, noise, use_prior) -> Dict[str, Tensor]:
     mp = map_encoder(model.mp_encoder, b["sc/mp_valid"], b["sc/mp_attr"], b["sc/mp_pose"], b["ref/mp_type"], tr)
     tl_tokens = tl_pre_compute(model.tl_encoder, b["gt/tl_valid"], b["sc/tl_attr"], b["sc/tl_pose"], mp)
     mp["_kv_cache"], tl_tokens["_kv_cache"] = {}, {}  # map K/V tables: once per training step, shared by all 90 steps
-    post = latent_posterior(model.latent_encoder, b, mp, tl_tokens, tr)
-    pr = model.latent_encoder.latent_dist_prior
-    valid_hist = b["sc/ag_valid"].any(-1)
-    prior = DiagGaussian(pr.mean.expand(*valid_hist.shape, -1), pr.log_std, valid=valid_hist)
+    le = model.latent_encoder
+    post = latent_dist(le, b, mp, tl_tokens, tr, posterior=True)
+    pr = le.latent_dist_prior
+    if pr.skip_forward:  # a fixed prior (std_gaus / std_cat): its encoders are not run
+        prior = pr(None, b["sc/ag_valid"].any(-1), b["ref/ag_type"])
+    else:  # a learned prior: a second differentiated encoder pass over the history, its dropout sites after the posterior's
+        prior = latent_dist(le, b, mp, tl_tokens, tr, posterior=False)
     # rsample with the noise drawn from the CPU generator, as the reference's CPU path does (same stream under the same
     # seed); one [n, A, 16] host-to-device copy per training step
-    if use_prior is None:
-        lat = prior if torch.rand(1) < hp.p_training_rollout_prior else post
-        l_mean, l_std, l_valid = lat.mean, lat.stddev, lat.valid
-    else:  # the same choice as a device-side select (no host branch inside a captured step)
-        l_mean = torch.where(use_prior, prior.mean, post.mean)
-        l_std = torch.where(use_prior, prior.stddev.expand_as(post.mean), post.stddev.expand_as(post.mean))
-        l_valid = torch.where(use_prior, prior.valid, post.valid)
-    if noise is None:
-        noise = torch.randn(l_mean.shape).to(l_mean.device)
-    z = l_mean + l_std * noise
+    if le.categorical:
+        # the straight-through Gumbel-max sample of the chosen side's logits (MultiCategorical.sample); noise: uniform in (0, 1)
+        if use_prior is None:
+            lat = prior if torch.rand(1) < hp.p_training_rollout_prior else post
+            l_logits, l_valid = lat.logits, lat.valid
+        else:  # (a device-side select between the two sides' parameters: no host branch inside a captured step)
+            l_logits = torch.where(use_prior, prior.logits.expand_as(post.logits), post.logits)
+            l_valid = torch.where(use_prior, prior.valid, post.valid)
+        if noise is None:
+            noise = torch.rand(l_logits.shape).clamp_(min=torch.finfo(torch.float32).tiny).to(l_logits.device)
+        z = MultiCategorical(l_logits).sample(False, noise=noise.view(l_logits.shape))
+    else:
+        if use_prior is None:
+            lat = prior if torch.rand(1) < hp.p_training_rollout_prior else post
+            l_mean, l_std, l_valid = lat.mean, lat.stddev, lat.valid
+        else:  # the same choice as a device-side select (no host branch inside a captured step)
+            l_mean = torch.where(use_prior, prior.mean, post.mean)
+            l_std = torch.where(use_prior, prior.stddev.expand_as(post.mean), post.stddev.expand_as(post.mean))
+            l_valid = torch.where(use_prior, prior.valid, post.valid)
+        if noise is None:
+            noise = torch.randn(l_mean.shape).to(l_mean.device)
+        z = l_mean + l_std * noise
     navi_pred = navi_predictor(model.navi_predictor, b, mp, tr)
     tf = wm.teacher_forcing_training
     tf.init(ag_valid=b["gt/ag_valid"], ag_pose=b["gt/ag_pose"], ag_motion=b["gt/ag_motion"], tl_state=b["gt/tl_state"],
