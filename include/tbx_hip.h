@@ -781,7 +781,8 @@ int tbx_rowchain_live(const tbx_stage_t* stages /* host */, int n_stages, int64_
  *   attr [n*A*W, 32]: size3 type3 | spd acc yaw_rate | one-hot_W(position) | 0-pad   (W <= 23)
  *   pe   [n*A*W, pe_dim]: pe_xy_yaw of the step's pose in the token frame, row_invalid [n*A*W] u8
  *   type_mask [3, n*A] u8: ~(type_i & valid_now)
- *   navi_pose3 [n*A, 3]: dest token pose relative to the agent's current pose; navi_row [n*A] i32 = b*M + dest
+ *   navi_pose3 [n*A, 3]: dest token pose relative to the agent's current pose (the window's LAST step, valid or not - not the token
+ *   pose); navi_row [n*A] i32 = (b / mp_batch_div) * M + dest: the row of mp_tok_pose [n / mp_batch_div, M, 3] it was read from
  */
 /* tbx_agent_prep's arguments (also tbx_heads_tail_t.next_prep): n_tok = n_batch * n_ag rows. Optional (NULL = off): type_mask (needs
  * ag_type_idx), dest (needs mp_tok_pose, navi_pose3, navi_row, n_mp > 0, mp_batch_div > 0). pe_dim in {64, 128}. */

@@ -488,7 +488,19 @@ __device__ __forceinline__ void agent_prep(const AgentPrepArgs& a, const int i, 
       dpx = a.mp_tok_pose[mrow * 3], dpy = a.mp_tok_pose[mrow * 3 + 1], dpyaw = a.mp_tok_pose[mrow * 3 + 2];
     }
   }
-  auto at = [&](const float f0, const float f1, const int idx) { return idx < 64 ? __shfl(f0, idx) : __shfl(f1, idx - 64); };
+  // float `idx` of the window out of the two registers. Both shuffles run with every lane of the wavefront active and the lanes only
+  // SELECT between them: a shuffle reads 0 from a lane that is masked off, and `idx < 64 ? shfl(f0) : shfl(f1)` as a branch masks off
+  // the lanes on its other side - among them, where a wavefront's indices straddle 64 (W = 22, 23: step 21 = floats 63..65, next to
+  // step 20 in the other slot), the lanes 0..4 that hold f1. `spill` is uniform: windows of up to 21 steps never pay the second shuffle.
+  const bool spill = 3 * W > 64;
+  auto at = [&](const float f0, const float f1, const int idx) {
+    float v = __shfl(f0, idx & 63);
+    if (spill) {
+      const float v1 = __shfl(f1, idx & 63);
+      v = idx < 64 ? v : v1;
+    }
+    return v;
+  };
   // ----------------------------------------------------------------
   const unsigned long long vmask = __ballot(hv_l);
   const int last = vmask ? 63 - __builtin_clzll(vmask) : -1;
