@@ -13,7 +13,16 @@ involved - and prints, per kernel,
     placed behind the loop it belongs in front of) is counted with the stage it follows in the file, not the one it runs in - a low
     wait in the last group of a kernel has to be looked up in the listing before it is blamed on that stage.
 
-    python tools/wait_audit.py [--src FILE] [--asm FILE.s [--rpass FILE]] [--kernel SUBSTRING] [--groups]
+  * with --paths (the default for any --src but dec_mid.hip, e.g. csrc/front.hip, whose kernels branch once into one of several
+    inlined bodies): the same counts per PATH, a path being the listing between two unconditional ends (s_branch, s_endpgm; pieces of
+    fewer than 300 instructions are left out) - with its vmcnt(0) waits, barriers and MFMAs, which tell the bodies apart (window +
+    projection: MFMAs and >= 10 barriers; rider: MFMAs and fewer barriers; search / pose embedding / dispatch: no MFMA), the scalar
+    loads at a REGISTER offset (an argument picked at run time; a constant offset is an immediate), the scalar loads that stand between
+    a barrier and the next global_load_dwordx4 of its interval (a unit request behind a scalar round trip), and its load groups.
+    s_cselect counts every scalar select - the K-nearest bisection's pivot update is one per key bit - so the selects of argument
+    offsets are read from the register-offset column, not from it.
+
+    python tools/wait_audit.py [--src FILE] [--asm FILE.s [--rpass FILE]] [--kernel SUBSTRING] [--groups] [--paths]
 
 --asm reads an assembly file made before (with --rpass: the compiler's remarks saved from that run) instead of compiling.
 --groups lists every load group; without it a kernel's groups are summarised as a histogram of their lowest waits."""
@@ -109,14 +118,53 @@ def audit(body):
     return r
 
 
+def paths(body):
+    """the listing's regions between two s_branch / s_endpgm, in listing order (blocks laid out of line are counted where they stand)"""
+    ins = [l for l in body if l and not l.startswith((".", ";")) and not l.endswith(":")]
+    out, cur = [], []
+    for l in ins:
+        cur.append(l)
+        if l.startswith(("s_endpgm", "s_branch")):
+            out.append(cur)
+            cur = []
+    if cur:
+        out.append(cur)
+    return out
+
+
+def path_row(ins):
+    r = audit(ins)
+    bars = sum(l.startswith("s_barrier") for l in ins)
+    mfma = sum(l.startswith("v_mfma") for l in ins)
+    vm0 = sum(1 for l in ins if l.startswith("s_waitcnt") and "vmcnt(0)" in l)
+    kind = ("window + projection" if bars >= 10 else "rider") if mfma else "search / embedding / dispatch"
+    # scalar loads between a barrier and the first wide vector load behind it (before the next barrier)
+    late, seen_bar, pending = 0, False, 0
+    for l in ins:
+        if l.startswith("s_barrier"):
+            seen_bar, pending = True, 0
+        elif seen_bar and l.startswith(("s_load", "s_buffer_load")):
+            pending += 1
+        elif seen_bar and l.startswith("global_load_dwordx4"):
+            late += pending
+            seen_bar, pending = False, 0
+    reg_off = sum(1 for l in ins if re.match(r"s_(buffer_)?load_\w+\s+\S+\s+\S+\s+s\d+", l.replace(",", " ")))
+    return r, bars, mfma, vm0, kind, late, reg_off
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--src", default=str(ROOT / "trafficbotsv1.5_amd" / "csrc" / "dec_mid.hip"))
     ap.add_argument("--asm")
     ap.add_argument("--rpass")
-    ap.add_argument("--kernel", default="dec_layer_mf", help="substring of the demangled kernel name")
+    ap.add_argument("--kernel", default=None, help="substring of the demangled kernel name (default: dec_layer_mf for dec_mid.hip, every kernel otherwise)")
     ap.add_argument("--groups", action="store_true")
+    ap.add_argument("--paths", action="store_true")
     a = ap.parse_args()
+    is_mid = pathlib.Path(a.src).name == "dec_mid.hip"
+    if a.kernel is None:
+        a.kernel = "dec_layer_mf" if is_mid else ""
+    a.paths = a.paths or not is_mid
     if a.asm:
         asm = pathlib.Path(a.asm).read_text()
         remarks = pathlib.Path(a.rpass).read_text() if a.rpass else ""
@@ -134,6 +182,19 @@ def main():
         u = res.get(sym, {})
         use = " ".join(u.get(k, "?") for k in ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]"))
         print(f"{name} | {r['head_waits']} / {r['head_s_load']} ({r['first_vmem_line']}) | {r['s_load']}, {r['lgkm0']}, {r['s_cselect']}, {r['n_ins']} | {use}")
+        if a.paths:
+            f = lambda v: "-" if v is None else v
+            for i, ins in enumerate(paths(body)):
+                if len(ins) < 300:  # (dispatch code, early returns, the out-of-line halves of cosf / sinf)
+                    continue
+                q, bars, mfma, vm0, kind, late, reg_off = path_row(ins)
+                print(f"    path {i} ({kind}): {q['n_ins']} instructions, s_load {q['s_load']} ({reg_off} at a register offset), lgkmcnt(0) {q['lgkm0']}, vmcnt(0) {vm0}, s_cselect {q['s_cselect']}, "
+                      f"barriers {bars}, mfma {mfma}; scalar waits / loads before its 1st vector load: {q['head_waits']} / {q['head_s_load']}; "
+                      f"s_load between a barrier and its next global_load_dwordx4: {late}")
+                for line, n, low, low_after, m in q["groups"]:
+                    print(f"        instruction {line:6d}: {n:2d} x global_load_dwordx4 ({m} mfma), lowest vmcnt before the next barrier: "
+                          f"{f(low)} behind the first load, {f(low_after)} behind the last")
+            continue
         if a.groups:
             for line, n, low, low_after, mfma in r["groups"]:
                 f = lambda v: "-" if v is None else v

@@ -8,6 +8,12 @@
 #include "../../include/tbx_hip.h"
 #include "tbx_common.h"
 
+// profiling build of csrc/front.hip (`make clk`): stage stamps of the front launch's bodies; nothing in any other build
+#ifndef TBX_FRONT_CLK
+#define TBX_FRONT_CLK(i)
+#define TBX_FRONT_CLK_LOADS()
+#endif
+
 namespace tbx_knn {
 
 struct KnnArgs {
@@ -33,7 +39,12 @@ __device__ __forceinline__ void rel_xy(float x1, float y1, float c, float s, flo
 
 // WPR = wavefronts per source row: the selection is done by the row's first wave, the K embeddings are split over all
 // WPR waves (4 on the small grids of a few scenes, where the kernel is latency-bound; 1 on large grids).
-template <int MAXC, int WPR>
+// EMB = false: the relative-pose form only (a.emb is not looked at, no barrier, no LDS) - csrc/front.hip, whose search workgroups
+// run on 256 of the workgroup's 512 threads.
+// The source row's pose, its invalid byte and every candidate field are requested in ONE clause: the candidates' addresses depend on the
+// row's index alone, and cosf / sinf of the row's yaw run under the candidates' flight (one memory round trip in front of the
+// bisection instead of one per dependent load).
+template <int MAXC, int WPR, bool EMB = true>
 __device__ __forceinline__ void knn_rows(const KnnArgs& a, int block) {
   constexpr int RPB = 4 / WPR;
   __shared__ float rel_s[RPB][64][3];
@@ -43,15 +54,17 @@ __device__ __forceinline__ void knn_rows(const KnnArgs& a, int block) {
   const int wir = wv % WPR;   // wave within the row
   const int row = block * RPB + wave;
   if (row >= a.n_rows) return;  // uniform per row (per workgroup when WPR == 4)
+  if constexpr (!EMB)
+    if (wir != 0) return;  // (the row's other waves only embed)
   const int b = row / a.n_src;
   const int bt = b / a.tgt_batch_div;
   const float x1 = a.src_pose[row * 3 + 0], y1 = a.src_pose[row * 3 + 1], yaw1 = a.src_pose[row * 3 + 2];
-  const bool inv1 = a.src_invalid[row] != 0;
-  const float c = cosf(yaw1), s = sinf(yaw1);
+  const uint8_t inv1_b = a.src_invalid[row];
   const float* tp = a.tgt_pose + (int64_t)bt * a.n_tgt * 3;
   const uint8_t* ti = a.tgt_invalid + (int64_t)bt * a.n_tgt;
 
   if (wir == 0) {
+    TBX_FRONT_CLK(16);
     // Candidate keys: the fp32 bits of the distance (non-negative, so unsigned order == float order; +inf for masked
     // pairs), 0xffffffff for slots past n_tgt. Lane l owns targets l, l+64, ...
     // The candidates' relative poses stay in registers from here to the output phase (rx, ry, yaw difference, the target's own
@@ -71,6 +84,10 @@ __device__ __forceinline__ void knn_rows(const KnnArgs& a, int block) {
         cyaw[q] = tp[j * 3 + 2];
         tb[q] = ti[j];
       }
+      TBX_FRONT_CLK_LOADS();
+      TBX_FRONT_CLK(17);
+      const bool inv1 = inv1_b != 0;
+      const float c = cosf(yaw1), s = sinf(yaw1);
 #pragma unroll
       for (int q = 0; q < MAXC; ++q) {
         const bool tin = tb[q] != 0;
@@ -92,6 +109,7 @@ __device__ __forceinline__ void knn_rows(const KnnArgs& a, int block) {
       for (int q = 0; q < MAXC; ++q) cnt += __popcll(__ballot(key[q] < cand));
       if (cnt < a.k) kth = cand;
     }
+    TBX_FRONT_CLK(18);
     // Everything below the K-th key is in; keys equal to it fill the remaining slots in ascending target index (the
     // reference's topk leaves the order among equal distances open; masked +inf pairs are don't-cares). Output slots
     // are assigned in ascending target index: position = number of chosen targets with a smaller index.
@@ -115,9 +133,11 @@ __device__ __forceinline__ void knn_rows(const KnnArgs& a, int block) {
         a.idx[o] = j;
         a.invalid[o] = (((tinv >> q) & 1u) != 0 || dist > a.dist_limit) ? 1 : 0;
         const float rx = crx[q], ry = cry[q], ryaw = cyaw[q];
-        rel_s[wave][pos][0] = rx;
-        rel_s[wave][pos][1] = ry;
-        rel_s[wave][pos][2] = ryaw;
+        if constexpr (EMB) {
+          rel_s[wave][pos][0] = rx;
+          rel_s[wave][pos][1] = ry;
+          rel_s[wave][pos][2] = ryaw;
+        }
         if (a.rel_pose != nullptr) {
           a.rel_pose[o * 3 + 0] = rx;
           a.rel_pose[o * 3 + 1] = ry;
@@ -127,7 +147,9 @@ __device__ __forceinline__ void knn_rows(const KnnArgs& a, int block) {
       ties_before += __popcll(tie_m);
       chosen_before += __popcll(take_m);
     }
+    TBX_FRONT_CLK(19);
   }  // wir == 0
+  if constexpr (!EMB) return;
   if (a.emb == nullptr) return;
   if constexpr (WPR > 1)
     __syncthreads();
@@ -156,28 +178,36 @@ struct KnnMulti {
   int n_jobs;
   PoseEmbedArgs pe;  // pe.n == 0: none
 };
+// the pose-embedding job's workgroup `block` (256 threads): one thread per (pose, argument) as pose_embed_kernel
+__device__ __forceinline__ void pose_embed_block(const PoseEmbedArgs& pe, const int block) {
+  const int half = pe.pe_dim >> 1;
+  const int64_t e = (int64_t)block * 256 + threadIdx.x;
+  if (e >= pe.n * half) return;
+  const int64_t i = e / half;
+  const int c = (int)(e - i * half);
+  tbx::pose_emb_write(pe.out + i * pe.ld + pe.col_off, pe.pe_dim, pe.pose3[i * 3], pe.pose3[i * 3 + 1], pe.pose3[i * 3 + 2], pe.fxy, pe.fyaw, c, half);
+}
+// one job's workgroup `block` in the 4-waves-per-row form: the body for the candidates per lane that n_tgt needs. BIG = false: the
+// caller has made sure that n_tgt <= 1024, and the 32-candidate body (it sets a kernel's register count) is not compiled in
+template <bool BIG, bool EMB>
+__device__ __forceinline__ void knn_job_block(const KnnArgs& a, const int block) {
+  if (a.n_tgt <= 128) {
+    knn_rows<2, 4, EMB>(a, block);
+  } else if (!BIG || a.n_tgt <= 1024) {
+    knn_rows<16, 4, EMB>(a, block);
+  } else {
+    if constexpr (BIG) knn_rows<32, 4, EMB>(a, block);
+  }
+}
 // `bid` = the workgroup's index among the launch's search / embedding workgroups, by 256 threads
 __device__ __forceinline__ void knn_multi_body(const KnnMulti& m, const int bid) {
-  if (bid >= m.first_block[KNN_MAX_JOBS]) {  // one thread per (pose, argument) as pose_embed_kernel
-    const int half = m.pe.pe_dim >> 1;
-    const int64_t e = (int64_t)(bid - m.first_block[KNN_MAX_JOBS]) * 256 + threadIdx.x;
-    if (e >= m.pe.n * half) return;
-    const int64_t i = e / half;
-    const int c = (int)(e - i * half);
-    tbx::pose_emb_write(m.pe.out + i * m.pe.ld + m.pe.col_off, m.pe.pe_dim, m.pe.pose3[i * 3], m.pe.pose3[i * 3 + 1], m.pe.pose3[i * 3 + 2],
-                        m.pe.fxy, m.pe.fyaw, c, half);
+  if (bid >= m.first_block[KNN_MAX_JOBS]) {
+    pose_embed_block(m.pe, bid - m.first_block[KNN_MAX_JOBS]);
     return;
   }
   int j = 0;
   while (j + 1 < m.n_jobs && bid >= m.first_block[j + 1]) ++j;
-  const KnnArgs& a = m.job[j];
-  const int block = bid - m.first_block[j];
-  if (a.n_tgt <= 128)
-    knn_rows<2, 4>(a, block);
-  else if (a.n_tgt <= 1024)
-    knn_rows<16, 4>(a, block);
-  else
-    knn_rows<32, 4>(a, block);
+  knn_job_block<true, true>(m.job[j], bid - m.first_block[j]);
 }
 
 

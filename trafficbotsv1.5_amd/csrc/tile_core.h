@@ -32,6 +32,12 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 #define TBX_GLOBAL __attribute__((address_space(1)))
 
+// profiling build of csrc/front.hip (`make clk`): stage stamps of the front launch's bodies; nothing in any other build
+#ifndef TBX_FRONT_CLK
+#define TBX_FRONT_CLK(i)
+#define TBX_FRONT_CLK_LOADS()
+#endif
+
 constexpr int NWAVE = 8, NT = NWAVE * 64, D = 128;
 constexpr int UNIT = TBX_MFMA32_UNIT_FLOATS;  // 2112 floats: 4 groups x (hi 1 KiB | lo 1 KiB) + 4 x 16 bias floats
 
@@ -193,15 +199,21 @@ __device__ __forceinline__ f32x4 gemv4(const W& w, const char* P, int lo, int st
   for (int st = 0; st < 4; ++st) step(acc, w.hi[st], w.lo[st], P, lo, st0 + st, g4);
   return acc.sum();
 }
-// LayerNorm of the 128-float row `src` (LDS) by one wavefront, in rowchain.hip's ln_row order -> planes (lo 256 bytes behind)
-__device__ __forceinline__ void ln_planes(const float* src, char* P, int lane, float eps, const float* gamma, const float* beta) {
-  float v[2], gm[2], bt[2];
+// the lane's LayerNorm parameters (columns lane, lane + 64): two loads each, requested by the caller ahead of whatever the LayerNorm's
+// stage requests itself (vmcnt retires in order: a wait for them then waits for nothing requested later)
+__device__ __forceinline__ void ln_params(const float* gamma, const float* beta, int lane, float (&gm)[2], float (&bt)[2]) {
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
-    v[q] = src[lane + 64 * q];
     gm[q] = *(const TBX_GLOBAL float*)(gamma + lane + 64 * q);
     bt[q] = *(const TBX_GLOBAL float*)(beta + lane + 64 * q);
   }
+}
+// LayerNorm of the 128-float row `src` (LDS) by one wavefront, in rowchain.hip's ln_row order -> planes (lo 256 bytes behind);
+// gm, bt = ln_params' values
+__device__ __forceinline__ void ln_planes(const float* src, char* P, int lane, float eps, const float (&gm)[2], const float (&bt)[2]) {
+  float v[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) v[q] = src[lane + 64 * q];
   const float mean = tbx::wave_sum(v[0] + v[1]) / 128.f;
   const float d0 = v[0] - mean, d1 = v[1] - mean;
   const float var = tbx::wave_sum(d0 * d0 + d1 * d1) / 128.f;
@@ -220,8 +232,11 @@ __device__ __forceinline__ void ln_planes(const float* src, char* P, int lane, f
 
 // the rider's tile (tbx_layer_tile_t.rider_*): four 128 -> 128 stages on 16 rows of its own, planes ping-pong Pa <-> Pb
 // (PL = the caller's plane geometry for 16 rows, K >= 128; X = 16 rows of XLD floats of LDS; Pa, Pb = plane pairs)
-template <class PL, int XLD>
-__device__ __forceinline__ void rider_tile(const tbx_layer_tile_t& t, int tile, float* X, char* Pa, char* Pb) {
+// T = tbx_layer_tile_t or a struct with its rider_* members (csrc/front.hip's compact argument group).
+// The rows' own loads (input or pose, rider_add, rider_valid) are requested in front of the two weight units: the first barrier waits
+// for the inputs only, not for the units behind them.
+template <class PL, int XLD, class T>
+__device__ __forceinline__ void rider_tile(const T& t, int tile, float* X, char* Pa, char* Pb) {
   constexpr int ROWS = 16;
   constexpr int PLANE = PL::PLANE;
   const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -233,27 +248,34 @@ __device__ __forceinline__ void rider_tile(const tbx_layer_tile_t& t, int tile, 
   const int64_t grow = row0 + (row_ok ? j : 0);
   const int aoff = PL::lane_off(lane, 0);
   const int c_out = 16 * wave + 4 * g;
+  TBX_FRONT_CLK(20);
+  const int r = tid >> 5, c4 = tid & 31;
+  const bool pose = t.rider_pose3 != nullptr;
+  const int64_t rin = row0 + (r < nv ? r : 0);  // (clamped: the tile's first row is always there)
+  float p3[3] = {0.f, 0.f, 0.f};
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (pose) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) p3[q] = *((const TBX_GLOBAL float*)t.rider_pose3 + rin * 3 + q);
+  } else {
+    v = gld4(t.rider_in + rin * D + c4 * 4);
+  }
+  const f32x4 add = gld4(t.rider_add + grow * D + c_out);
+  const bool ok = *(const TBX_GLOBAL uint8_t*)(t.rider_valid + grow) != 0;
   W wb[2];
   load_unit(wb[0], t.rider_images[0], wave, lane);
   load_unit(wb[1], t.rider_images[1], wave, lane);
-  const f32x4 add = gld4(t.rider_add + grow * D + c_out);
-  const bool ok = *(const TBX_GLOBAL uint8_t*)(t.rider_valid + grow) != 0;
   {
-    const int r = tid >> 5, c4 = tid & 31;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (t.rider_pose3 != nullptr) {  // the rows' pose embeddings (tbx_common.h pose_emb_write: the stand-alone kernel's values)
-      if (r < nv) {
-        const TBX_GLOBAL float* p3 = (const TBX_GLOBAL float*)t.rider_pose3 + (row0 + r) * 3;
-        tbx::pose_emb_write(X + r * XLD, D, p3[0], p3[1], p3[2], t.rider_freqs_xy, t.rider_freqs_yaw, c4, 32);
-      }
+    if (pose) {  // the rows' pose embeddings (tbx_common.h pose_emb_write: the stand-alone kernel's values)
+      if (r < nv) tbx::pose_emb_write(X + r * XLD, D, p3[0], p3[1], p3[2], t.rider_freqs_xy, t.rider_freqs_yaw, c4, 32);
       __syncthreads();
       if (r < nv) v = *(const f32x4*)(X + r * XLD + c4 * 4);
-    } else if (r < nv) {
-      v = gld4(t.rider_in + (row0 + r) * D + c4 * 4);
     }
+    if (r >= nv) v = (f32x4){0.f, 0.f, 0.f, 0.f};
     planes_write4<PL>(Pa, r, c4 * 4, v);
   }
   __syncthreads();
+  TBX_FRONT_CLK(21);
   {
     Acc acc;
     acc.zero();
@@ -263,6 +285,7 @@ __device__ __forceinline__ void rider_tile(const tbx_layer_tile_t& t, int tile, 
     load_unit(wb[0], t.rider_images[2], wave, lane);
   }
   __syncthreads();
+  TBX_FRONT_CLK(22);
   {
     Acc acc;
     acc.zero();
@@ -272,6 +295,7 @@ __device__ __forceinline__ void rider_tile(const tbx_layer_tile_t& t, int tile, 
     load_unit(wb[1], t.rider_images[3], wave, lane);
   }
   __syncthreads();
+  TBX_FRONT_CLK(23);
   {
     Acc acc;
     acc.zero();
@@ -280,6 +304,7 @@ __device__ __forceinline__ void rider_tile(const tbx_layer_tile_t& t, int tile, 
     planes_write4<PL>(Pb, j, c_out, relu4(acc.sum() + wb[0].bias));
   }
   __syncthreads();
+  TBX_FRONT_CLK(24);
   {
     Acc acc;
     acc.zero();
@@ -289,6 +314,7 @@ __device__ __forceinline__ void rider_tile(const tbx_layer_tile_t& t, int tile, 
     if (!ok) v = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (row_ok) gst4(t.rider_out + grow * D + c_out, v);
   }
+  TBX_FRONT_CLK(25);
 }
 
 

@@ -22,7 +22,8 @@ struct WindowArgs {
 template <int DM, bool ADD>
 __global__ __launch_bounds__(NT) void tile_window_kernel(const WindowArgs a) {
   extern __shared__ __attribute__((aligned(16))) char lds_c[];
-  window_body<DM, ADD>(a.t, (int)blockIdx.x, lds_c, nullptr);
+  if (a.t.drop_thresh != 0u) window_body<DM, ADD, true>(a.t, (int)blockIdx.x, lds_c, nullptr);  // (training's stepping pass)
+  else window_body<DM, ADD, false>(a.t, (int)blockIdx.x, lds_c, nullptr);
 }
 
 }  // namespace
