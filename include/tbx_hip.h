@@ -148,7 +148,8 @@ typedef struct tbx_attn_args {
                                fold_image = tbx_pack_weight_gemv(linear_rpe.weight[128:256], linear_rpe.bias[128:256], n = 32, k = 128,
                                groups = 4): 66 KiB, fetched into LDS by LDS-DMA while the targets are swept. 128 floats per row leave the
                                kernel instead of 640, and the grouped LINEAR stage that applied the fold in the following chain
-                               disappears; the result is bit-identical to that stage's (same fma order). Inference only: with
+                               disappears; the result is bit-identical to that stage's (same fma order) in every row with a valid
+                               target (rows without one: zeros, where the stage would leave the bias). Inference only: with
                                p_drop > 0 the call returns TBX_ERR_UNSUPPORTED. */
   /* backward (tbx_knarpe_attn_bwd). Probabilities are recomputed from the forward inputs; the pose embeddings carry no gradient
    * (utils/rpe.py:7). */
@@ -179,6 +180,24 @@ typedef struct tbx_attn_args {
  * closed loop at one or a few scenes): 4 wavefronts share a row; large launches: a wavefront per row. fp32 or bfloat16 K/V tables
  * (bfloat16: no dropout). */
 int tbx_knarpe_attn_fwd(const tbx_attn_t* args /* host */, void* stream);
+
+/* Which kernel form tbx_knarpe_attn_fwd would launch for `args`: the launchers' own decision (one host function in csrc/attn.hip
+ * makes it for both), after the same argument checks in the same order. Dereferences no pointer of `args` but `args` itself,
+ * launches nothing, needs no GPU (the folded form's grid cap then assumes 256 CUs). Returns the negative code the call would return,
+ * or one of TBX_ATTN_FORM_SPLIT4 / _WAVE / _RING (value & TBX_ATTN_FORM_MASK) with the flags that hold for the launch ORed on. */
+enum {
+  TBX_ATTN_FORM_SPLIT4 = 1,       /* knarpe_attn_kernel, 4 wavefronts share a source row: a workgroup per row */
+  TBX_ATTN_FORM_WAVE = 2,         /* knarpe_attn_kernel, a wavefront per row: 4 rows per workgroup */
+  TBX_ATTN_FORM_RING = 3,         /* knarpe_attn_ring_kernel: a wavefront per row, K / V rows through a per-wave LDS ring */
+  TBX_ATTN_FORM_MASK = 0xF,
+  TBX_ATTN_FORM_DROP = 0x10,      /* the dropout instantiation (p_drop > 0) */
+  TBX_ATTN_FORM_KV16 = 0x20,      /* bfloat16 K/V tables */
+  TBX_ATTN_FORM_FOLD = 0x40,      /* fold_image: the value fold in the epilogue, 128 floats per row */
+  TBX_ATTN_FORM_FOLD_LOOP = 0x80, /* FOLD | WAVE with the grid capped below the row quads: a workgroup walks more than one quad */
+  TBX_ATTN_FORM_BATCH_MAJOR = 0x100, /* WAVE: a workgroup's 4 rows are one source token of 4 consecutive batch entries (shared tables) */
+  TBX_ATTN_FORM_XCD = 0x200       /* workgroups take their rows in the XCD-contiguous order (not the folded wave-per-row form) */
+};
+int tbx_knarpe_attn_fwd_form(const tbx_attn_t* args /* host */);
 
 /* The forward of LARGE launches (a wavefront per source row) on the bf16 matrix cores (csrc/attn_mfma.hip): scores and
  * weighted sums as v_mfma_f32_16x16x32_bf16 products per source row (heads padded 4 -> 16), the pair's embedding evaluated in the

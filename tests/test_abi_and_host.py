@@ -20,8 +20,8 @@ def hip(tb):
 
 def test_library_exports_every_declared_symbol(hip):
     """One library, one symbol list: the tbx_* functions libtbx_hip.so exports are exactly the entry points include/tbx_hip.h and the four
-    topical headers it includes declare - 72 in its own text (ABI 7 as it was laid down) + 1 / 3 / 1 / 1 added since -, each bound with
-    argtypes, and the package names no other library."""
+    topical headers it includes declare - 73 in its own text (ABI 7 as it was laid down + tbx_knarpe_attn_fwd_form) + 1 / 3 / 1 / 1 added
+    since -, each bound with argtypes, and the package names no other library."""
     import re
     import subprocess
 
@@ -33,12 +33,12 @@ def test_library_exports_every_declared_symbol(hip):
                          "tbx_loss_shape", "tbx_tf_threshold"}
     nm = subprocess.run(["nm", "-D", "--defined-only", str(hip.LIB_PATH)], check=True, capture_output=True, text=True).stdout
     exported = [l.split()[2] for l in nm.splitlines() if len(l.split()) == 3 and l.split()[1] == "T" and l.split()[2].startswith("tbx_")]
-    assert sorted(exported) == sorted(syms) and len(syms) == 78
+    assert sorted(exported) == sorted(syms) and len(syms) == 79
     # ... counted header by header, each from its own text
     main = hip.HEADER_PATH.read_text()
     decl = r"^(?:int|int64_t|const char\*)\s+(tbx_\w+)\s*\("
     count = lambda txt: len(set(re.findall(decl, txt, flags=re.M)))
-    assert count(main) == 72
+    assert count(main) == 73
     for name, n in (("tbx_hip_metrics.h", 1), ("tbx_hip_reward.h", 3), ("tbx_hip_loss.h", 1), ("tbx_hip_tf.h", 1)):
         assert f'#include "{name}"' in main and count((hip.HEADER_PATH.parent / name).read_text()) == n, name
     for s in syms:

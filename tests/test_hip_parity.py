@@ -312,15 +312,16 @@ def test_split_bf16_linear_close_to_exact_fp32_linear(hip, dev, rows, k, n, grou
     assert float((err / mag).max()) < 3e-5, float((err / mag).max())
 
 
-@pytest.mark.parametrize("n", [32, 16])  # 2048 rows: a wave per row, plain gathers; 1024 rows: one wave per SIMD -> the LDS-ring kernel
+@pytest.mark.parametrize("n", [32, 16])  # 2048 rows: a wave per row, plain gathers; 1024 rows, relative poses: the LDS-ring kernel
 @pytest.mark.parametrize("mode", ["rel", "emb", "rel_dropout"])
 def test_attention_large_grid_kernel_matches_small_grid_kernel(tb, hip, dev, mode, n):
-    """Grids of >= 1024 rows run one wavefront per row, smaller ones four wavefronts per row merged through LDS (checked
-    against the oracle above): the same 2048 rows as one launch and as four 512-row launches must agree - two segments with
-    shared tables (batch_div), masked pairs, a row without a valid target, in-register and materialised embeddings, and the
-    dropout mask (keyed by the launch-local row index, hence compared on the first quarter only)."""
+    """Large grids (>= 193 rows, with dropout >= 1024) run one wavefront per row, smaller ones four wavefronts per row merged through
+    LDS (checked against the oracle above): the same 2048 / 1024 rows as one launch and as launches of 128 rows (with dropout: 512)
+    must agree - two segments with shared tables (batch_div), masked pairs, a row without a valid target, in-register and
+    materialised embeddings, and the dropout mask (keyed by the launch-local row index, hence compared on the first chunk only).
+    Both sides' forms are asked of the library (hip.knarpe_attn_form)."""
     g = torch.Generator().manual_seed(12)
-    S, T1, T2, K1, K2, div = 64, 128, 96, 25, 9, 8
+    S, T1, T2, K1, K2, div = 64, 128, 96, 25, 9, 2
     rows = n * S
     P = import_module("trafficbots_amd.utils.pose_emb")
     pe = P.PoseEmb("pe_xy_yaw", pe_dim=128, theta_xy=1e3).to(dev)
@@ -351,12 +352,15 @@ def test_attention_large_grid_kernel_matches_small_grid_kernel(tb, hip, dev, mod
                        emb=e2[sl].contiguous() if emb else None, rel=None if emb else rel2[sl].contiguous(), batch_div=div)
         out = torch.empty(nb * S, 640, device=dev)
         flag = torch.empty(nb * S, dtype=torch.uint8, device=dev)
-        hip.knarpe_attn(qbuf[b0 * S:(b0 + nb) * S], 0, 128, bias, nb, S, [seg1, seg2], out, flag, None if emb else fx, None if emb else fy,
-                        drop=drop)
-        return out, flag
+        args = (qbuf[b0 * S:(b0 + nb) * S], 0, 128, bias, nb, S, [seg1, seg2], out, flag, None if emb else fx, None if emb else fy)
+        hip.knarpe_attn(*args, drop=drop)
+        return out, flag, hip.knarpe_attn_form(*args, drop=drop) & hip.ATTN_FORM_MASK
 
-    big, flag_big = run(0, n)                      # 2048 / 1024 rows: a wave per row
-    parts = [run(b0, 8) for b0 in range(0, n, 8)]  # 512 rows each: four waves per row
+    big, flag_big, form_big = run(0, n)  # 2048 / 1024 rows: a wave per row
+    assert form_big == (hip.ATTN_FORM_RING if n == 16 and not emb else hip.ATTN_FORM_WAVE)
+    nb = 8 if drop is not None else 2  # 512 rows (below the 1024 of launches with dropout) / 128 rows (below 193): four waves per row
+    parts = [run(b0, nb) for b0 in range(0, n, nb)]
+    assert all(p[2] == hip.ATTN_FORM_SPLIT4 for p in parts)
     n_cmp = 1 if drop is not None else len(parts)  # the dropout counter uses the launch's own row numbering
     small = torch.cat([p[0] for p in parts[:n_cmp]])
     flag_small = torch.cat([p[1] for p in parts[:n_cmp]])
@@ -445,12 +449,13 @@ def test_live_row_chain_is_bit_identical_to_mfma_tiles(tb, live, rows):
         assert torch.equal(a, b), (name, float((a - b).abs().max()))
 
 
-@pytest.mark.parametrize("S", [33, 1030])  # 1030: n * S >= 1024 rows -> the wave-per-row form (4 rows per workgroup, ragged tail)
+@pytest.mark.parametrize("S", [33, 1030])  # 1030: n * S >= 1024 rows -> the wave-per-row forms (4 rows per workgroup) and the quad loop
 @pytest.mark.parametrize("bf16", [False, True])
 def test_folded_attention_epilogue_equals_the_fold_stage(tb, bf16, S):
     """tbx_knarpe_attn_fwd with fold_image (the value half of linear_rpe applied in the attention kernel's epilogue, 128 floats per row
     out) vs tbx_knarpe_attn_fwd's 640-wide row followed by the grouped LINEAR stage that applied the fold so far: bit-identical
-    (same fma order), rows without a valid target flagged the same - for a one-segment and a two-segment call."""
+    (same fma order), rows without a valid target flagged the same and exactly zero (the stage leaves the bias there; every consumer
+    skips them by the flag) - for a one-segment and a two-segment call. Both sides' forms are asked of the library."""
     hip = import_module("trafficbots_amd.hip")
     eng = import_module("trafficbots_amd.engine")
     M = import_module("trafficbots_amd.models.modules")
@@ -472,6 +477,9 @@ def test_folded_attention_epilogue_equals_the_fold_stage(tb, bf16, S):
     for segs in ([hip.Seg(kv, 0, 128, T, i1, m1, e1)], [hip.Seg(kv, 0, 128, T, i1, m1, e1), hip.Seg(kv2, 0, 128, 40, i2, m2, e2)]):
         o640, f640 = torch.empty(n * S, 640, device=dev), torch.empty(n * S, dtype=torch.uint8, device=dev)
         hip.knarpe_attn(q, 0, 128, att.linear_rpe.bias, n, S, segs, o640, f640)
+        kv16f = hip.ATTN_FORM_KV16 if bf16 else 0  # both sides' forms, asked of the library
+        form = (hip.ATTN_FORM_WAVE if S == 1030 else hip.ATTN_FORM_SPLIT4) | kv16f
+        assert hip.knarpe_attn_form(q, 0, 128, att.linear_rpe.bias, n, S, segs, o640, f640) & ~hip.ATTN_FORM_XCD == form
         want = torch.empty(n * S, d, device=dev)
         ch = hip.Chain(16, 644)
         ch.load(o640, hip.BUF0, 0, n=640)
@@ -480,8 +488,12 @@ def test_folded_attention_epilogue_equals_the_fold_stage(tb, bf16, S):
         ch.run(n * S)
         o128, f128 = torch.full((n * S, d), 7.0, device=dev), torch.empty(n * S, dtype=torch.uint8, device=dev)
         hip.knarpe_attn(q, 0, 128, att.linear_rpe.bias, n, S, segs, o128, f128, fold=eng.attn_fold_image(att))
+        assert (hip.knarpe_attn_form(q, 0, 128, att.linear_rpe.bias, n, S, segs, o128, f128, fold=eng.attn_fold_image(att))
+                & ~hip.ATTN_FORM_XCD == form | hip.ATTN_FORM_FOLD | (hip.ATTN_FORM_FOLD_LOOP if S == 1030 else 0))
         assert torch.equal(f128, f640) and int(f640.sum()) >= 1
-        assert torch.equal(o128, want), float((o128 - want).abs().max())
+        live = f640 == 0  # rows without a valid target: zeros (include/tbx_hip.h), where the stage leaves the fold of the zero row - the bias
+        assert torch.equal(o128[live], want[live]), float((o128[live] - want[live]).abs().max())
+        assert not o128[~live].any() and torch.equal(want[~live], att.linear_rpe.bias[d:].expand_as(want[~live]))
 
 
 @pytest.mark.parametrize("S,Ks,T,K,n_cross,bf16", [(8, 4, 64, 8, 1, False), (64, 25, 1024, 64, 1, False), (64, 36, 128, 24, 2, False),
@@ -1111,11 +1123,12 @@ def test_heads_tile_raw_with_keyed_dropout_equals_the_two_chains(tb, hip, dev, r
 def test_attention_lds_ring_equals_small_launches(hip, dev, bf16, K0, K1):
     """The LDS-ring form of the wave-per-row attention kernel (large launches: K / V rows of the next passes in flight as LDS-DMA
     gathers into a per-wave ring, target indices held in registers; csrc/attn.hip) against the same rows launched in chunks below
-    1024 rows (4 wavefronts per row, plain gathers): the same per-pair arithmetic, merged in a different order - 1e-5 of the largest
-    output. One or two segments, segments past 64 targets (second index register), shared tables (batch_div), bf16 tables,
-    rows without a valid target (exact zeros + flag)."""
+    193 rows (4 wavefronts per row, plain gathers): the same per-pair arithmetic, merged in a different order - 1e-5 of the largest
+    output. One or two segments, segments past 64 targets (second index register), shared tables (batch_div), bf16 tables (which take
+    the plain wave-per-row kernel by default: the bf16 ring is opt-in), rows without a valid target (exact zeros + flag). Both sides'
+    forms are asked of the library (hip.knarpe_attn_form)."""
     g = torch.Generator().manual_seed(K0 * 7 + K1)
-    n, S, T0, T1, D = 4, 300, 300, 500, 128
+    n, S, T0, T1, D = 16, 75, 300, 500, 128
     rows = n * S
     qbuf = torch.randn(rows, 640, generator=g).to(dev)
     bias = torch.randn(128, generator=g).to(dev)
@@ -1136,13 +1149,16 @@ def test_attention_lds_ring_equals_small_launches(hip, dev, bf16, K0, K1):
         nb = (r1 - r0) // S
         segs = [hip.Seg(kv[(r0 // S // div) * T:], 0, D, T, idx[r0 // S:r1 // S].contiguous(), inv[r0 // S:r1 // S].contiguous(), None, div,
                         rel=rel[r0 // S:r1 // S].contiguous()) for kv, idx, inv, rel, T, div in specs]
-        hip.knarpe_attn(qbuf[r0:r1], 0, D, bias, nb, S, segs, out[r0:r1], flag[r0:r1], fxy, fyw)
+        args = (qbuf[r0:r1], 0, D, bias, nb, S, segs, out[r0:r1], flag[r0:r1], fxy, fyw)
+        hip.knarpe_attn(*args)
+        return hip.knarpe_attn_form(*args) & (hip.ATTN_FORM_MASK | hip.ATTN_FORM_KV16)
 
     big, bflag = torch.full((rows, 640), 3.0, device=dev), torch.full((rows,), 9, dtype=torch.uint8, device=dev)
-    run(0, rows, big, bflag)  # 1200 rows: the ring kernel
+    # 1200 rows: the ring kernel (fp32 tables)
+    assert run(0, rows, big, bflag) == (hip.ATTN_FORM_WAVE | hip.ATTN_FORM_KV16 if bf16 else hip.ATTN_FORM_RING)
     small, sflag = torch.full((rows, 640), 5.0, device=dev), torch.full((rows,), 9, dtype=torch.uint8, device=dev)
-    for r0 in range(0, rows, 2 * S):  # 600 rows per launch: 4 waves per row (batch entries in pairs: batch_div = 2 stays aligned)
-        run(r0, r0 + 2 * S, small, sflag)
+    for r0 in range(0, rows, 2 * S):  # 150 rows per launch: 4 waves per row (batch entries in pairs: batch_div = 2 stays aligned)
+        assert run(r0, r0 + 2 * S, small, sflag) == hip.ATTN_FORM_SPLIT4 | (hip.ATTN_FORM_KV16 if bf16 else 0)
     torch.cuda.synchronize()
     assert torch.equal(bflag, sflag) and int(bflag[S + 5]) == 1
     assert float(big[S + 5].abs().max()) == 0.0

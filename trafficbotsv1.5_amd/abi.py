@@ -39,6 +39,9 @@ F_MASKED_SUM = 16384
 F_ROWZERO = 32768
 BUF0, BUF1, AUX, GLOBAL = 0, 1, 2, 3
 MAX_STAGES, AUX_LD = 44, 260
+# TBX_ATTN_FORM_* (tbx_knarpe_attn_fwd_form): the kernel form in the low bits, flags ORed on
+ATTN_FORM_SPLIT4, ATTN_FORM_WAVE, ATTN_FORM_RING, ATTN_FORM_MASK = 1, 2, 3, 0xF
+ATTN_FORM_DROP, ATTN_FORM_KV16, ATTN_FORM_FOLD, ATTN_FORM_FOLD_LOOP, ATTN_FORM_BATCH_MAJOR, ATTN_FORM_XCD = 0x10, 0x20, 0x40, 0x80, 0x100, 0x200
 
 
 class Stage(C.Structure):
@@ -320,6 +323,7 @@ def load():
     lib.tbx_rel_pose_dense.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.tbx_diffbar_reward.argtypes = [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, vp]
     lib.tbx_knarpe_attn_fwd.argtypes = [C.POINTER(Attn), vp]
+    lib.tbx_knarpe_attn_fwd_form.argtypes = [C.POINTER(Attn)]
     lib.tbx_knarpe_attn_fwd_mfma.argtypes = [C.POINTER(Attn), vp]
     lib.tbx_knarpe_attn_bwd.argtypes = [C.POINTER(Attn), vp]
     lib.tbx_knarpe_dec_mid.argtypes = [C.POINTER(DecMid), vp]

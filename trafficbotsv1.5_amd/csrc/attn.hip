@@ -91,6 +91,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPR == 1 ? 
   __shared__ float red_s[WPR > 1 ? WPR : 1][WPR > 1 ? (OUTW + 2 * NH) : 1];
   __shared__ __attribute__((aligned(16))) float fold_s[FOLD ? FOLD_ROWS * D * 4 : 4];  // 66 KiB: the fold image, by LDS-DMA
   __shared__ __attribute__((aligned(16))) float comb_s[FOLD ? (WPR == 1 ? 4 : 1) * OUTW : 1];  // WPR == 1: the workgroup's 4 rows
+  __shared__ int valid_s[FOLD && WPR == 1 ? 4 : 1];  // ... and whether each has a valid target: the folded row of one without is zeros
   if constexpr (FOLD) {
     // the image is requested first and lands while the targets are swept: 1 KiB per wave instruction, straight into LDS (asm:
     // the compiler would order every later LDS read behind a DMA it knows of - see csrc/rowchain.hip gemv_dma)
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPR == 1 ? 
       em.scale(inv_l);
       em.store(&comb_s[rib * OUTW + D + hq * DR], s8);
     }
-    if (lane == 0) a.row_no_valid[row] = any_valid ? 0 : 1;
+    if (lane == 0) a.row_no_valid[row] = any_valid ? 0 : 1, valid_s[rib] = any_valid ? 1 : 0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of the fold image have landed
     __syncthreads();
     const int c = threadIdx.x & (D - 1), r0 = threadIdx.x >> 7, h = c / DH;
@@ -189,9 +190,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPR == 1 ? 
       ra = (int64_t)(4 * (quad / a.n_src) + r0) * a.n_src + quad % a.n_src;
       rb = ra + 2 * (int64_t)a.n_src;
     }
-    if (ra < a.n_rows) a.out[ra * a.ldo + c] = acc0;
-    if (rb < a.n_rows) a.out[rb * a.ldo + c] = acc1;
-    __syncthreads();  // comb_s is rewritten by the next quad
+    // (a row without a valid target: zeros as in the 640-wide form, not the fold of the zero row, which is the bias)
+    if (ra < a.n_rows) a.out[ra * a.ldo + c] = valid_s[r0] ? acc0 : 0.f;
+    if (rb < a.n_rows) a.out[rb * a.ldo + c] = valid_s[r0 + 2] ? acc1 : 0.f;
+    __syncthreads();  // comb_s and valid_s are rewritten by the next quad
   } else if constexpr (WPR == 1) {
     const bool any_valid = M[0] > -INFINITY;  // masks are per target, so every head sees the same validity
     if ((lane & 8) == 0) {
@@ -247,7 +249,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPR == 1 ? 
       if (threadIdx.x < D) {
         const int c = threadIdx.x, h = c / DH;
         const float acc = gemv_chain(fold_s, c, comb_s + D + h * DR, DR / 16, fold_s[c * 4] + comb_s[c]);
-        orow[c] = acc;
+        orow[c] = any_valid ? acc : 0.f;  // (a row without a valid target: zeros as in the 640-wide form, not the bias)
       }
     } else {
       for (int c = threadIdx.x; c < OUTW; c += 256) {
@@ -846,21 +848,56 @@ static int attn_big_rows(bool dropout = true) {
   return dropout ? big_rows : big_rows_infer;
 }
 
-// the 640-wide row (t.fold_image == NULL), with or without dropout
-static int launch_fwd(AttnArgs& a, const tbx_attn_t& t, hipStream_t hs) {
+// TBX_ATTN_RING: 0 the default below, 1 the ring for every launch it can serve, 2 its R = 2 form (measured: no gain)
+static int attn_ring_mode() {
+  static const int v = [] { const char* e = getenv("TBX_ATTN_RING"); return e ? atoi(e) : 0; }();
+  return v;
+}
+
+// THE dispatch decision of tbx_knarpe_attn_fwd, made once for launch_fwd, launch_fwd_folded and tbx_knarpe_attn_fwd_form: which
+// kernel form the checked call `a` (fill_args + set_drop) takes, as a TBX_ATTN_FORM_* code with its flags (include/tbx_hip.h), or the
+// error of a combination no kernel is built for. *grid: the workgroups of the launch. Host arithmetic only.
+static int fwd_form(const AttnArgs& a, const tbx_attn_t& t, int* grid) {
   const tbx_attn_seg_t* segs = t.seg;
-  const int n_seg = t.n_seg;
-  const bool big = a.n_rows >= attn_big_rows(a.drop_thresh != 0u);  // a wave per row from here on (below: 4 waves split a row's targets)
-  const dim3 grid(big ? (a.n_rows + 3) / 4 : a.n_rows), block(256);
+  const bool fold = t.fold_image != nullptr, drop = a.drop_thresh != 0u, kv16 = segs[0].kv_bf16 != 0;
+  const int quads = (a.n_rows + 3) / 4;
+  int flags = (drop ? TBX_ATTN_FORM_DROP : 0) | (kv16 ? TBX_ATTN_FORM_KV16 : 0) | (fold ? TBX_ATTN_FORM_FOLD : 0);
+  if (fold) {  // the value fold in the epilogue: inference only
+    if (drop) return TBX_ERR_UNSUPPORTED;
+    const bool big = a.n_rows >= attn_big_rows();  // a wave per row from here on, 4 rows per workgroup
+    if (!big) {
+      *grid = a.n_rows;
+      return TBX_ATTN_FORM_SPLIT4 | flags | (a.xcd ? TBX_ATTN_FORM_XCD : 0);
+    }
+    // the persistent quad loop (at most fold_grid_max() workgroups) walks the quads in the plain order: no XCD map
+    *grid = quads < fold_grid_max() ? quads : fold_grid_max();
+    return TBX_ATTN_FORM_WAVE | flags | (quads > *grid ? TBX_ATTN_FORM_FOLD_LOOP : 0) | (a.batch_major ? TBX_ATTN_FORM_BATCH_MAJOR : 0);
+  }
+  const bool big = a.n_rows >= attn_big_rows(drop);  // a wave per row from here on (below: 4 waves split a row's targets)
+  *grid = big ? quads : a.n_rows;
+  flags |= a.xcd ? TBX_ATTN_FORM_XCD : 0;
   // the LDS-ring form (opt-in, TBX_ATTN_RING=1 / 2): large launches without dropout whose segments are all given as relative poses
-  static const int ring_mode = [] { const char* e = getenv("TBX_ATTN_RING"); return e ? atoi(e) : 0; }();  // measured: no gain, opt-in
   // ... and, by default, launches that leave every SIMD with at most ONE wave (<= 1024 rows a wave per row: training's stepping pass,
   // 16 scenes x 64 agents): a lone wave has no partner to hide its gathers behind, the ring does (24 -> ~9 us per launch)
   static const int ring_lone_rows = [] { const char* e = getenv("TBX_ATTN_RING_LONE_ROWS"); return e ? atoi(e) : 1536; }();
-  const bool lone = big && a.n_rows <= ring_lone_rows && segs[0].kv_bf16 == 0;
-  bool ring_ok = big && (ring_mode != 0 || lone) && (a.drop_thresh == 0u || segs[0].kv_bf16 == 0);
-  for (int i = 0; i < n_seg; ++i) ring_ok = ring_ok && segs[i].rel_pose != nullptr && segs[i].emb == nullptr && segs[i].k <= 128 && segs[i].k > 0;
-  if (ring_ok) {
+  const bool lone = big && a.n_rows <= ring_lone_rows && !kv16;
+  bool ring_ok = big && (attn_ring_mode() != 0 || lone) && (!drop || !kv16);
+  for (int i = 0; i < t.n_seg; ++i) ring_ok = ring_ok && segs[i].rel_pose != nullptr && segs[i].emb == nullptr && segs[i].k <= 128 && segs[i].k > 0;
+  if (ring_ok) return TBX_ATTN_FORM_RING | flags;
+  if (kv16 && drop) return TBX_ERR_UNSUPPORTED;  // bf16 K/V tables: inference only
+  if (!big) return TBX_ATTN_FORM_SPLIT4 | flags;
+  return TBX_ATTN_FORM_WAVE | flags | (a.batch_major ? TBX_ATTN_FORM_BATCH_MAJOR : 0);
+}
+
+// the 640-wide row (t.fold_image == NULL), with or without dropout
+static int launch_fwd(AttnArgs& a, const tbx_attn_t& t, hipStream_t hs) {
+  int n_wg = 0;
+  const int form = fwd_form(a, t, &n_wg);
+  if (form < 0) return form;
+  const dim3 grid(n_wg), block(256);
+  const bool big = (form & TBX_ATTN_FORM_MASK) != TBX_ATTN_FORM_SPLIT4;
+  const bool drop = (form & TBX_ATTN_FORM_DROP) != 0, kv16 = (form & TBX_ATTN_FORM_KV16) != 0;
+  if ((form & TBX_ATTN_FORM_MASK) == TBX_ATTN_FORM_RING) {
 #define TBX_RING_LAUNCH(KV16F, RF, WPEF, DROPF)                                                                                   \
   do {                                                                                                                            \
     constexpr int bytes = 4 * (RF) * RingGeom<KV16F>::SLOT;                                                                       \
@@ -873,24 +910,23 @@ static int launch_fwd(AttnArgs& a, const tbx_attn_t& t, hipStream_t hs) {
     }                                                                                                                             \
     hipLaunchKernelGGL((knarpe_attn_ring_kernel<KV16F, RF, WPEF, DROPF>), grid, block, bytes, hs, a);                             \
   } while (0)
-    if (segs[0].kv_bf16 != 0)
+    if (kv16)
       TBX_RING_LAUNCH(true, 4, 2, false);
-    else if (a.drop_thresh != 0u)
+    else if (drop)
       TBX_RING_LAUNCH(false, 4, 1, true);
-    else if (ring_mode == 2)
+    else if (attn_ring_mode() == 2)
       TBX_RING_LAUNCH(false, 2, 2, false);
     else
       TBX_RING_LAUNCH(false, 4, 1, false);
 #undef TBX_RING_LAUNCH
     return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
   }
-  if (segs[0].kv_bf16 != 0) {  // bf16 K/V tables: inference only
-    if (a.drop_thresh != 0u) return TBX_ERR_UNSUPPORTED;
+  if (kv16) {
     if (big)
       hipLaunchKernelGGL((knarpe_attn_kernel<1, false, true>), grid, block, 0, hs, a);
     else
       hipLaunchKernelGGL((knarpe_attn_kernel<4, false, true>), grid, block, 0, hs, a);
-  } else if (a.drop_thresh != 0u) {
+  } else if (drop) {
     if (big)
       hipLaunchKernelGGL((knarpe_attn_kernel<1, true>), grid, block, 0, hs, a);
     else
@@ -906,13 +942,14 @@ static int launch_fwd(AttnArgs& a, const tbx_attn_t& t, hipStream_t hs) {
 
 // the value fold in the epilogue (t.fold_image): 128 floats per row, inference only
 static int launch_fwd_folded(AttnArgs& a, const tbx_attn_t& t, hipStream_t hs) {
-  if (a.drop_thresh != 0u) return TBX_ERR_UNSUPPORTED;
+  int n_wg = 0;
+  const int form = fwd_form(a, t, &n_wg);
+  if (form < 0) return form;
   a.ldo = t.ldo;
   a.fold_img = t.fold_image;
-  const bool big = a.n_rows >= attn_big_rows();  // a wave per row from here on, 4 rows per workgroup
-  const int quads = (a.n_rows + 3) / 4;
-  const dim3 grid(big ? (quads < fold_grid_max() ? quads : fold_grid_max()) : a.n_rows), block(256);
-  if (t.seg[0].kv_bf16 != 0) {
+  const dim3 grid(n_wg), block(256);
+  const bool big = (form & TBX_ATTN_FORM_MASK) == TBX_ATTN_FORM_WAVE;
+  if (form & TBX_ATTN_FORM_KV16) {
     if (big)
       hipLaunchKernelGGL((knarpe_attn_kernel<1, false, true, true>), grid, block, 0, hs, a);
     else
@@ -926,18 +963,33 @@ static int launch_fwd_folded(AttnArgs& a, const tbx_attn_t& t, hipStream_t hs) {
   return hipGetLastError() == hipSuccess ? TBX_OK : TBX_ERR_LAUNCH;
 }
 
-extern "C" int tbx_knarpe_attn_fwd(const tbx_attn_t* t, void* stream) {
+// tbx_knarpe_attn_fwd's argument checks, in its order: a = the checked call (out / row_no_valid still to be set), *fold = its row width
+static int check_fwd(AttnArgs& a, const tbx_attn_t* t, bool* fold) {
   if (!t || !t->out || !t->row_no_valid) return TBX_ERR_ARG;
-  const bool fold = t->fold_image != nullptr;
-  if ((((uintptr_t)t->out) & 15) || (fold && ((((uintptr_t)t->fold_image) & 15) || (t->ldo & 3) || t->ldo < D))) return TBX_ERR_ALIGN;
-  AttnArgs a;
-  int rc = fill_args(a, *t, fold ? D + NH * DR : t->ldo);  // (the folded row's own width was checked above)
+  *fold = t->fold_image != nullptr;
+  if ((((uintptr_t)t->out) & 15) || (*fold && ((((uintptr_t)t->fold_image) & 15) || (t->ldo & 3) || t->ldo < D))) return TBX_ERR_ALIGN;
+  const int rc = fill_args(a, *t, *fold ? D + NH * DR : t->ldo);  // (the folded row's own width was checked above)
   if (rc != TBX_OK) return rc;
-  rc = set_drop(a, *t);
+  return set_drop(a, *t);
+}
+
+extern "C" int tbx_knarpe_attn_fwd(const tbx_attn_t* t, void* stream) {
+  AttnArgs a;
+  bool fold = false;
+  const int rc = check_fwd(a, t, &fold);
   if (rc != TBX_OK) return rc;
   a.out = t->out;
   a.row_no_valid = t->row_no_valid;
   return fold ? launch_fwd_folded(a, *t, (hipStream_t)stream) : launch_fwd(a, *t, (hipStream_t)stream);
+}
+
+extern "C" int tbx_knarpe_attn_fwd_form(const tbx_attn_t* t) {
+  AttnArgs a;
+  bool fold = false;
+  const int rc = check_fwd(a, t, &fold);
+  if (rc != TBX_OK) return rc;
+  int n_wg = 0;
+  return fwd_form(a, *t, &n_wg);
 }
 
 extern "C" int tbx_knarpe_attn_bwd(const tbx_attn_t* t, void* stream) {

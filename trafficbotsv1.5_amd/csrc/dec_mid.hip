@@ -322,7 +322,7 @@ __global__ __launch_bounds__(NW * 64) void dec_mid_kernel(const MidArgs a) {
     const float f = combine_fold(st, M, L, red_s, comb_s, slot_a, wir, lane, s8, tg, valid2, NT);
     if (a.wo2 == nullptr) {
       if (threadIdx.x < D) {
-        a.out2[(int64_t)row * a.ld_out2 + threadIdx.x] = f;
+        a.out2[(int64_t)row * a.ld_out2 + threadIdx.x] = valid2 ? f : 0.f;  // tbx_knarpe_attn_fwd's folded row: zeros without a valid target
         a.x[(int64_t)row * D + threadIdx.x] = xs[threadIdx.x];  // the token row after the self-attention residual
       }
       if (threadIdx.x == 0) a.flag2[row] = valid2 ? 0 : 1;

@@ -129,6 +129,20 @@ def knarpe_attn(qbuf, q_off: int, qt_off: int, rpe_k_bias, n_batch: int, n_src: 
     _check(load().tbx_knarpe_attn_fwd(C.byref(a), stream_ptr()), "tbx_knarpe_attn_fwd")
 
 
+def knarpe_attn_form(qbuf, q_off: int, qt_off: int, rpe_k_bias, n_batch: int, n_src: int, segs: Sequence[Seg], out, row_no_valid,
+                     freqs_xy=None, freqs_yaw=None, drop=None, fold=None) -> int:
+    """tbx_knarpe_attn_fwd_form for knarpe_attn's arguments: the ATTN_FORM_* code (form | flags) of the kernel that call would launch,
+    or the negative tbx code it would raise on. Nothing is launched and no tensor is read: host tensors of the call's shapes will do
+    (no GPU needed)."""
+    hip_base._HOST_PTRS = True
+    try:
+        a = _attn_args(qbuf, q_off, qt_off, rpe_k_bias, n_batch, n_src, segs, (freqs_xy, freqs_yaw), drop)
+        a.out, a.ldo, a.row_no_valid, a.fold_image = _ptr(out, torch.float32), out.stride(0), _ptr(row_no_valid, torch.uint8), _ptr(fold, torch.float32)
+    finally:
+        hip_base._HOST_PTRS = False
+    return int(load().tbx_knarpe_attn_fwd_form(C.byref(a)))
+
+
 def knarpe_attn_mfma(qbuf, q_off: int, qt_off: int, n_batch: int, n_src: int, segs: Sequence[Seg], out, row_no_valid, freqs_xy, freqs_yaw,
                      drop=None):
     """tbx_knarpe_attn_fwd_mfma: the wave-per-row forward on the bf16 matrix cores (bf16 operands, fp32 accumulation / softmax).
